@@ -4,8 +4,8 @@
 Contract (driver):  python bench.py --gpus N --steps K --warmup W
 For N > 1 it runs one rank per GPU under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* from the environment); rank 0 prints ONE JSON line. Started DIRECTLY with --gpus N > 1
-(no WORLD_SIZE in the environment) it launches those N ranks itself -- it re-executes under
-`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` -- or
+(no WORLD_SIZE in the environment) it launches those N ranks itself -- it runs
+`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` as a child -- or
 exits non-zero when the node has fewer than N GPUs; a line never claims more GPUs than ranks ran
 (world_size == n_gpus == len(per_rank), one distinct device per rank, asserted before printing).
 
@@ -31,6 +31,10 @@ metric  = solver iterations/s: executions of the IRLS loop body (reference Front
           (max over ranks).  frames/s is reported beside it.
 Multi-GPU: independent streams per GPU (no data-path collective), weak scaling; the line carries world_size and the
 per-rank rates so that the rank count RCCL saw can be checked from the output.
+
+--dump-outputs DIR: rank 0 writes what the LAST timed step of every block returned to its caller (timed_outputs) as
+DIR/<block>_<name>.npy, float32 / float64, a few MB. The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import hashlib
@@ -46,6 +50,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+MAX_FRAMES_PER_LAUNCH = 4096  # sf_process_frames / sf_process_sequence_frames_device refuse more frames in one launch
 
 WORKLOAD_TEXT = {
     "static": ("BASELINE.json configs[1]: synthetic static RGB-D pairs, VGA->QVGA 320x240, 3-level pyramid, "
@@ -89,7 +94,14 @@ def parse():
     ap.add_argument("--pass-reps", type=int, default=4, help="repetitions of each isolated IRLS pass (roofline.irls_passes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed in every block as DIR/<block>_<name>.npy")
+    args = ap.parse_args()
+    if not 1 <= args.steps <= MAX_FRAMES_PER_LAUNCH:  # the K timed steps are one launch of K frames (sf_process_frames)
+        ap.error("--steps must be between 1 and %d" % MAX_FRAMES_PER_LAUNCH)
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def make_params(api, workload):
@@ -223,15 +235,22 @@ def _free_port():
     return port
 
 
+def _visible_gpus():
+    """GPUs this node exposes, counted in a child process: the launcher itself never opens the device."""
+    code = "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"
+    try:
+        return int(subprocess.check_output([sys.executable, "-c", code], stderr=subprocess.DEVNULL, timeout=300).split()[-1])
+    except Exception:
+        return 0
+
+
 def self_launch_if_needed(args):
-    """`python bench.py --gpus N` started directly (WORLD_SIZE unset) with N > 1: one process cannot be N ranks. Re-execute
-    under torch.distributed.run with N ranks on this node, or fail loudly when the node does not have N GPUs.
+    """`python bench.py --gpus N` started directly (WORLD_SIZE unset) with N > 1: one process cannot be N ranks. Run the N ranks
+    under torch.distributed.run in a child process and exit with its status, or fail loudly when the node does not have N GPUs.
     (SF_BENCH_SINGLE_GPU=1, the one-GPU test hook that puts every rank on cuda:0, lifts the device-count check.)"""
     if "WORLD_SIZE" in os.environ or args.gpus <= 1:
         return
-    import torch
-
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    have = _visible_gpus()
     if have < args.gpus and not os.environ.get("SF_BENCH_SINGLE_GPU"):
         sys.stderr.write("bench.py: --gpus %d requested but this node exposes %d GPU(s); refusing to print a line for GPUs that did not run\n"
                          % (args.gpus, have))
@@ -240,7 +259,7 @@ def self_launch_if_needed(args):
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stderr.write("bench.py: launching %d ranks: %s\n" % (args.gpus, " ".join(cmd)))
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 class Harness:
@@ -369,6 +388,7 @@ def run_pairs_workload(hx, args, workload, batch, with_parity):
     shader_mhz = solver.shader_clock_mhz(clk0, solver.shader_clock_counters())
     frames_timed, iters_total, pix_total = c1[0] - c0[0], c1[1] - c0[1], c1[3] - c0[3]
     assert frames_timed == B * args.steps, (frames_timed, B, args.steps)
+    outputs = timed_outputs(solver) if args.dump_outputs else None  # before the un-timed step below overwrites them
     k_ms = region_ms / args.steps
     solver.process_frame(im)  # per-stage unit counts of ONE launch (for the algorithmic byte count): one more, un-timed step
     stats_last = [solver.stats(b) for b in range(min(B, args.distinct))]
@@ -442,6 +462,7 @@ def run_pairs_workload(hx, args, workload, batch, with_parity):
             "irls_passes": irls_passes,
         },
         "pairs": pairs,
+        "outputs": outputs,
     }
 
 
@@ -483,6 +504,54 @@ def isolated_passes(solver, B, n0, reps, copy_gbs=None):
     return out
 
 
+DUMP_SAMPLE_STREAMS = 64  # --dump-outputs: streams whose per-stream results are read back (a fixed, seeded sample of the batch)
+DUMP_IMAGE_STREAMS = 4  # ... of which the first few also give their level-0 images
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(solver):
+    """What the last timed step handed its caller, read back after the timed region (--dump-outputs): pose and iteration counts of
+    every stream; twist, b field and per-cluster residuals of a fixed, seeded sample of streams; b image and level-0 cluster
+    labels of the first streams of that sample. float32 / float64 only (counts and labels converted exactly), all finite: the
+    library reports a cluster without valid pixels with a NaN residual (sf_residuals.h), written here as 0 in
+    `cluster_residuals` and 1 in `cluster_empty`."""
+    B = solver.batch_size
+    T, n_irls, n_outer, pix = solver.batch_results()
+    sample = np.sort(np.random.default_rng(20240601).choice(B, size=min(B, DUMP_SAMPLE_STREAMS), replace=False))
+    img = sample[:DUMP_IMAGE_STREAMS]
+    res = np.stack([solver.cluster_residuals(b) for b in sample])
+    empty = np.isnan(res)
+    return {
+        "T": T.astype(np.float32),
+        "n_irls": n_irls.astype(np.float64),
+        "n_outer": n_outer.astype(np.float64),
+        "pixel_iters": pix.astype(np.float64),
+        "sample_streams": sample.astype(np.float64),
+        "twist": np.stack([solver.twist(b) for b in sample]),
+        "b": np.stack([solver.b(b) for b in sample]),
+        "cluster_residuals": np.where(empty, np.float32(0.0), res),
+        "cluster_empty": empty.astype(np.float32),
+        "b_image": np.stack([solver.b_image(b) for b in img]),
+        "labels0": np.stack([solver.labels(0, b) for b in img]).astype(np.float32),
+    }
+
+
+def dump_outputs(directory, blocks):
+    """Write every block's timed_outputs() as DIR/<block>_<name>.npy. Returns (files, bytes)."""
+    arrays = {"%s_%s" % (block, name): a for block, outs in blocks for name, a in outs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB, more than the %d MB allowed" % (total / 2**20, DUMP_MAX_BYTES >> 20))
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if not np.isfinite(a).all():
+            raise SystemExit("bench.py: --dump-outputs: %s holds %d non-finite values" % (name, int((~np.isfinite(a)).sum())))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return len(arrays), total
+
+
 def _cached_sequence(seed, F, pool):
     """One synthetic sequence as (d [F][n0], i [F][n0], T_gt) -- from /tmp when a run on this node has rendered it before (the
     driver runs N = 1, 2, 4, 8 back to back: rank r's seeds at N recur at 2 N), else rendered and stored. The cache key
@@ -499,7 +568,8 @@ def synthetic_sequence_pool(hx, args):
     quota only contend), and a sequence rendered once on this node is read back from /tmp."""
     import multiprocessing as mp
 
-    D, F = args.seq_distinct, args.seq_frames
+    # a run of more steps than the sequences hold gets longer sequences (run_sequences_workload plays frames 0 .. warmup + steps + 8)
+    D, F = args.seq_distinct, max(args.seq_frames, args.warmup + args.steps + 10)
     cap = cgroup_cpu_limit()
     cpus = len(os.sched_getaffinity(0)) if cap is None else max(1, min(len(os.sched_getaffinity(0)), int(cap)))
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(hx.world)))
@@ -638,6 +708,7 @@ def run_sequences_workload(hx, args, B, pool):
     frames_timed, iters_total = c1[0] - c0[0], c1[1] - c0[1]
     assert frames_timed == B * args.steps
     T_after_timed = solver.batch_results()[0].copy()  # pose of the last timed frame of every stream (sequences_parity)
+    outputs = timed_outputs(solver) if args.dump_outputs else None  # before the un-timed frames below
     first_timed, last_timed = step - args.steps, step - 1
     # kernel duration: the timed launch itself (HIP events on the handle's stream around it) / its frames; launch-per-frame
     # mode and the unit counts: three more, un-timed launches
@@ -742,6 +813,7 @@ def run_sequences_workload(hx, args, B, pool):
             "kernel_ms_avg": kms,
         },
         "pairs": None,
+        "outputs": outputs,
     }
 
 
@@ -826,6 +898,11 @@ def main():
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args.workload, min(args.cpu_seconds, 8.0), lib)
             if full is not None:
                 out["full_solver"]["cpu_baseline"] = cpu_baseline("sphere", full["pairs"], min(args.cpu_seconds, 8.0), lib)
+        if args.dump_outputs:
+            blocks = [(args.workload, blk)] + ([("full_solver", full)] if full is not None else [])
+            blocks += [("sequences%d_b%d" % (q_i, q["config"]["streams_per_gpu"]), q) for q_i, q in enumerate(seq_blocks)]
+            n_files, n_bytes = dump_outputs(args.dump_outputs, [(name, b["outputs"]) for name, b in blocks])
+            sys.stderr.write("bench.py: %d arrays (%.1f MB) of the last timed step written to %s\n" % (n_files, n_bytes / 2**20, args.dump_outputs))
         out["wall_s"] = round(time.time() - t_main, 1)  # this process, argument parsing to this line (set-up, every block, the CPU legs)
         print(json.dumps(out))
     hx.close()

@@ -60,6 +60,18 @@ def hip_auto():
     return sf.load()
 
 
+def hip_runtime():
+    """The HIP runtime the product library is bound to, for the tests' own hipMalloc / hipMemcpy / hipStreamCreate (ctypes). The
+    symbols are looked up through libsf_hip.so's handle, i.e. in the copy of libamdhip64 that library resolved when it was loaded.
+    A plain CDLL("libamdhip64.so") can name ANOTHER copy: torch's wheel bundles its own, and a process that imports torch after
+    loading the product library holds both -- memory and streams of that copy are not the product's, and it may see no device."""
+    import ctypes
+
+    import staticfusion_amd as sf
+
+    return ctypes.CDLL(sf.LIB)
+
+
 def _pairs():
     from staticfusion_amd.synth import make_pair
 

@@ -35,7 +35,9 @@ class DevicePool:
 
     def __init__(self, host):
         if DevicePool._rt is None:
-            DevicePool._rt = ctypes.CDLL("libamdhip64.so")
+            import staticfusion_amd as sf
+
+            DevicePool._rt = ctypes.CDLL(sf.LIB)  # the HIP runtime the product library is bound to (conftest.hip_runtime)
         rt = DevicePool._rt
         self.ptr = ctypes.c_void_p()
         host = np.ascontiguousarray(host)

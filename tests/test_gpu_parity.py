@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, config2_params, driver_params, make_solver, trace_array
+from conftest import GOLDEN, config2_params, driver_params, hip_runtime, make_solver, trace_array
 from staticfusion_amd import capi
 from staticfusion_amd.synth import DEFAULT_XI, Scene, pose_delta, quantise_and_decimate, se3_exp
 
@@ -383,7 +383,7 @@ def test_device_resident_inputs_and_counters(hip, pair):
     s = make_solver(hip, 120, 160, config2_params(hip, levels=3), pr, batch=B)
     s.process_frame(0)
     T_host, n_irls, _, _ = s.batch_results()
-    hiprt = ctypes.CDLL("libamdhip64.so")
+    hiprt = hip_runtime()
     n = 120 * 160
     col = lambda a: np.ascontiguousarray(np.tile(np.asarray(a, np.float32).T.ravel(), B))
     bufs = []

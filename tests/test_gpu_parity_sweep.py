@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import config2_params, driver_params, make_solver
+from conftest import config2_params, driver_params, hip_runtime, make_solver
 from staticfusion_amd import capi
 from staticfusion_amd.synth import DEFAULT_XI, LCG64, Scene, pose_delta, se3_exp
 from test_gpu_parity import POSE_TOL, assert_traces_match, solve_both
@@ -214,7 +214,7 @@ def test_parameter_setters_and_external_hip_stream(hip, ora, pair):
     assert not np.array_equal(c.T(), res["hip"][0])
     assert c.last_solver_kernel_ms() > 0.0
     # caller-owned stream
-    hiprt = C.CDLL("libamdhip64.so")
+    hiprt = hip_runtime()
     st = C.c_void_p()
     assert hiprt.hipStreamCreate(C.byref(st)) == 0
     d = make_solver(hip, 120, 160, driver_params(hip, kb=1.3, max_iter_irls=4, ctf_levels=4), pr)

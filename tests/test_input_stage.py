@@ -14,7 +14,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, driver_params, make_solver
+from conftest import GOLDEN, driver_params, hip_runtime, make_solver
 from staticfusion_amd import capi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools", "golden"))
@@ -159,7 +159,7 @@ def test_hip_input_stage_batch_device_buffers_and_solver_handover(hip, ora):
 
     B, H, W, res = 3, 240, 320, 2
     frames = [synth_frame(H, W, 10 + b) for b in range(B)]
-    hiprt = C.CDLL("libamdhip64.so")
+    hiprt = hip_runtime()
     col = np.ascontiguousarray(np.stack([f[0] for f in frames]))
     dep = np.ascontiguousarray(np.stack([f[1] for f in frames]))
     ptrs = []

@@ -10,7 +10,7 @@ of slow ones and consecutive frames of a stream land on different CUs), checking
 import numpy as np
 import pytest
 
-from conftest import driver_params, make_solver
+from conftest import driver_params, hip_runtime, make_solver
 from staticfusion_amd import capi
 from staticfusion_amd.synth import DEFAULT_XI, make_sequence, pose_delta
 
@@ -74,7 +74,7 @@ def test_sequences_from_the_pool_in_one_launch(hip, ora):
     streams over two sequences; per-frame poses against the one-by-one loop (bit for bit) and against the oracle (<= 1e-4)."""
     import ctypes
 
-    hiprt = ctypes.CDLL("libamdhip64.so")
+    hiprt = hip_runtime()
 
     class Dev:  # a device copy of a host array (plain hipMalloc: the tests use no torch)
         def __init__(self, h):
@@ -166,11 +166,15 @@ def test_pool_arguments_are_checked(hip, pair):
 
     import staticfusion_amd as sf
 
-    hiprt = ctypes.CDLL("libamdhip64.so")
+    hiprt = hip_runtime()
     s = make_solver(hip, 60, 80, driver_params(hip), pair(seed=3, rows=60, cols=80, sphere=True), batch=2)
     n0 = 60 * 80
     ptr = ctypes.c_void_p()
     assert hiprt.hipMalloc(ctypes.byref(ptr), ctypes.c_size_t(4 * n0 * 3 + 64)) == 0
+    # defined contents, distinct in every frame and at every offset: fresh device memory may hold NaNs, which would fail the
+    # comparison below whether or not a refused call launched anything
+    fill = np.arange(n0 * 3 + 16, dtype=np.float32)
+    assert hiprt.hipMemcpy(ptr, fill.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(fill.nbytes), 1) == 0
     base = ptr.value
     ok = np.array([0, 2], np.int32)
     s.advance_sequences_device(base, base, ok, 3)
@@ -200,7 +204,7 @@ def test_a_launch_that_gave_up_on_streams_leaves_nothing_dangling(hip, monkeypat
 
     if hip.default_variant == "cluster":
         pytest.skip("the cluster build runs such calls frame by frame: no frame waits for another inside a launch")
-    hiprt = ctypes.CDLL("libamdhip64.so")
+    hiprt = hip_runtime()
     D, F, K, B = 2, 8, 6, 64
     seqs = [make_sequence(2100 + q, F, sphere=True, out_rows=60, out_cols=80) for q in range(D)]
     col = lambda a: np.ascontiguousarray(np.asarray(a, np.float32).T).ravel()

@@ -1,6 +1,6 @@
 """How well does a stream's IRLS iteration count of one frame predict the next? (the key of sf_order_kernel)"""
 import sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import staticfusion_amd as sf
 from staticfusion_amd.synth import make_sequence
