@@ -309,7 +309,7 @@ __device__ __forceinline__ void gst(gptr<T> p, int idx, V v) {
 // then complete in this XCD's L2 and a cell is written back once, when its line is evicted. Agent scope (what a cluster
 // of workgroups on different CUs needs) makes every atomic write through to the fabric: the zero store AND the sums both
 // reached HBM, 34 bytes written per pixel and warp where 16 are needed (profiles/r02j_traffic_by_stage.txt).
-#if defined(SF_CLUSTER) || defined(SF_ACC_AGENT)
+#ifdef SF_CLUSTER
 #define SF_ACC_SCOPE __HIP_MEMORY_SCOPE_AGENT
 #else
 #define SF_ACC_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
@@ -440,29 +440,21 @@ __device__ __forceinline__ long long mul_packed_w(int jf, int w) {
 }
 
 // depth / intensity of a target pixel from its fixed-point accumulators: sum(w * value) / sum(w).
-// The integer sums are exact; one int64 -> float conversion and one IEEE float division round twice
+// The integer sums are exact; one int64 -> float conversion and one float division round twice
 // (<= 1 ulp from the exact quotient, the same order as the reference's own float accumulation).
 // The two quotients share the divisor (an integer in [1, 2^20], exact in float): one hardware reciprocal (1 ulp), refined
 // by a Newton step, and a residual correction per quotient -- the correctly rounded quotient in all but a vanishing share
 // of the cases, within 1 ulp always, at a third of the instructions of two IEEE division sequences.
-#ifndef SF_FAST_NORMALISE
-#define SF_FAST_NORMALISE 1
-#endif
 __device__ __forceinline__ void normalise_acc(long long sd, long long packed, float &dw, float &iw) {
     const long long si = (long long)((unsigned long long)packed << (64 - ACC_W_SHIFT)) >> (64 - ACC_W_SHIFT);
     const float wf = (float)(unsigned)((packed - si) >> ACC_W_SHIFT);
     const float nd = (float)sd * (1.f / 67108864.f), ni = (float)si * (1.f / FIX_INTENS);
-#if SF_FAST_NORMALISE
     float r = __builtin_amdgcn_rcpf(wf);
     r = fmaf(fmaf(-wf, r, 1.f), r, r);
     float q = nd * r;
     dw = fmaf(fmaf(-wf, q, nd), r, q);
     q = ni * r;
     iw = fmaf(fmaf(-wf, q, ni), r, q);
-#else
-    dw = nd / wf;
-    iw = ni / wf;
-#endif
 }
 
 // initializeKMeans (reference KMeans.cpp:63-101): the seed a level-1 pixel starts with is the nearest of 24 seed positions
@@ -494,22 +486,15 @@ __device__ __forceinline__ unsigned km_nearest_seed(int rows_km, int cols_km, un
 //  Integer sums => the result is independent of both orders.
 // ---------------------------------------------------------------------------------------------
 #define SPLAT_TV 64
-#ifndef SPLAT_TU
 #define SPLAT_TU ((SF_NT == 256 ? 4 : 2) * SF_NT / 64)
-#endif
 #define SPLAT_PX ((SPLAT_TV * SPLAT_TU) / SF_NT)  // source pixels per lane and tile
-#ifndef SPLAT_MARGIN
 #define SPLAT_MARGIN 6  // window cells beyond the tile size in each direction (a rigid warp is locally a shift: rarely more)
-#endif
 #define WIN_V (SPLAT_TV + SPLAT_MARGIN)
 #define WIN_U (SPLAT_TU + SPLAT_MARGIN)
 #define WIN_CELLS (WIN_V * WIN_U)
 
 #define SPLAT_MAX_LAZY_TILES 512
 #define SPLAT_LAZY_COLS 640  // lazy mode keeps a row watermark per accumulator column (SplatMarks)
-#ifndef SF_SPLAT_FRESH
-#define SF_SPLAT_FRESH 1
-#endif
 struct SplatWin {
     long long d[WIN_CELLS];
     long long i[WIN_CELLS];  // packed like the global cell
@@ -526,10 +511,7 @@ struct SplatWin {
 // instead of being zeroed first and added to afterwards. The tiles walk down a strip of SPLAT_TU columns and then move
 // right, so the watermark of a column only grows. Targets outside a tile's window (rare: strong local stretch) cannot go
 // straight to the global cells -- their cell may not be initialised yet -- so the tile is flagged and replayed after the
-// last tile. (-DSF_SPLAT_FRESH=0: the round-2 form -- zero the columns a window reaches first, atomics for every cell.)
-#ifndef SF_SPLAT_BOX
-#define SF_SPLAT_BOX 1  // 0: the flush walks the whole window (round 4)
-#endif
+// last tile.
 struct SplatMarks {
     unsigned short zrow[SPLAT_LAZY_COLS];
 };
@@ -546,12 +528,9 @@ __device__ __forceinline__ void tiled_splat(const SplatGeom &g, int rows_i, int 
     const int lane = tid & 63;
     const int tiles_v = (rows_i + SPLAT_TV - 1) / SPLAT_TV, tiles_u = (cols_i + SPLAT_TU - 1) / SPLAT_TU;
     const int n_tiles = tiles_v * tiles_u;
-    int zcol = 0;  // lazy: accumulator columns [0, zcol) are zero or hold sums already
     if (lazy) {
         if (tid < SPLAT_MAX_LAZY_TILES / 32) win.ovf[tid] = 0;  // ordered before its first use by the tile loop's barriers
-#if SF_SPLAT_FRESH
         for (int c = tid; c < cols_i; c += SF_NT) marks.zrow[c] = 0;
-#endif
     }
     // the rows [from, to) of column c, for every lane that raises `flag`, zeroed by the whole wave (call it wave-uniformly)
     auto zero_flagged = [&](bool flag, int c, int from, int to) {
@@ -568,26 +547,19 @@ __device__ __forceinline__ void tiled_splat(const SplatGeom &g, int rows_i, int 
     // lazy: a second walk over the tiles (it >= n_tiles) replays the flagged ones for their out-of-window targets
     for (int it = tile_first; it < (lazy ? 2 * n_tiles : n_tiles); it += tile_step) {  // a cluster's workgroups take every G-th tile
         const bool replay = it >= n_tiles;
-        if (SF_SPLAT_FRESH && pend_u0 >= 0) {  // (the flush that read the watermarks ended with a barrier)
+        if (pend_u0 >= 0) {  // (the flush that read the watermarks ended with a barrier)
             if (tid < pend_nu && pend_u0 + tid < cols_i && pend_z > (int)marks.zrow[pend_u0 + tid]) marks.zrow[pend_u0 + tid] = (unsigned short)pend_z;
             pend_u0 = -1;
         }
         const int tile = replay ? it - n_tiles : it;
         if (replay) {
             if (it == n_tiles) {  // every tile flushed: zero what no window reached; the flags are complete
-#if SF_SPLAT_FRESH
                 __syncthreads();  // the last window's watermarks (set at the top of this trip) are visible
                 for (int c0 = 0; c0 < cols_i; c0 += SF_NT) {  // a lane per column; a column short of the last row is rare
                     const int c = c0 + tid;
                     const int z = c < cols_i ? (int)marks.zrow[c] : rows_i;
                     zero_flagged(z < rows_i, c, z, rows_i);
                 }
-#else
-                for (int idx = zcol * rows_i + tid; idx < cols_i * rows_i; idx += SF_NT) {
-                    gst(acc_d, idx, 0ll);
-                    gst(acc_i, idx, 0ll);
-                }
-#endif
                 __syncthreads();
             }
             if (!((uniform_i((int)win.ovf[tile >> 5]) >> (tile & 31)) & 1)) continue;
@@ -646,7 +618,7 @@ __device__ __forceinline__ void tiled_splat(const SplatGeom &g, int rows_i, int 
         SF_DPP_REDUCE(utop, dpp_i32, sf_op_maxi)
         const int vmin = 0x7fffffff - __builtin_amdgcn_readlane(vtop, 63), umin = 0x7fffffff - __builtin_amdgcn_readlane(utop, 63);
         int vlast = 0, ulast = 0;
-        if (SF_SPLAT_BOX && lazy) {  // (uniform)
+        if (lazy) {  // (uniform)
             SF_DPP_REDUCE(vbot, dpp_i32, sf_op_maxi)
             SF_DPP_REDUCE(ubot, dpp_i32, sf_op_maxi)
             vlast = __builtin_amdgcn_readlane(vbot, 63) - 1;
@@ -656,24 +628,13 @@ __device__ __forceinline__ void tiled_splat(const SplatGeom &g, int rows_i, int 
         if (lane == 0) {
             lds_min(&win.vmin, vmin);
             lds_min(&win.umin, umin);
-            if (SF_SPLAT_BOX && lazy) {
+            if (lazy) {
                 __hip_atomic_fetch_max(&win.vmax, vlast, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_fetch_max(&win.umax, ulast, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
         __syncthreads();
         const int wv0 = uniform_i(win.vmin), wu0 = uniform_i(win.umin);
-        if (!SF_SPLAT_FRESH && lazy && !replay && wu0 != 0x7fffffff) {  // zero the columns this window reaches first (stores ordered
-                                                                        // before the flush's atomics by the barrier in front of phase 3)
-            const int need = min(cols_i, wu0 + WIN_U);
-            if (need > zcol) {
-                for (int idx = zcol * rows_i + tid; idx < need * rows_i; idx += SF_NT) {
-                    gst(acc_d, idx, 0ll);
-                    gst(acc_i, idx, 0ll);
-                }
-                zcol = need;
-            }
-        }
         bool outside = false;  // lazy: this lane had a target outside the window
         // ---- phase 2: splat into the window (LDS atomics), or straight to global if outside
         auto add = [&](int v, int u, int w, long long df, int jf) {
@@ -727,7 +688,7 @@ __device__ __forceinline__ void tiled_splat(const SplatGeom &g, int rows_i, int 
         }
         __syncthreads();
         // ---- phase 3: add the touched cells to the global accumulators (consecutive lanes -> consecutive v)
-        if (SF_SPLAT_FRESH && lazy) {
+        if (lazy) {
             if (!replay && wu0 != 0x7fffffff) {  // (no valid source pixel in the tile: nothing to flush, no column reached)
                 // Groups of 16 lanes take 16 rows that start on a multiple of 16 (a 128-byte line of cells where the level's
                 // rows are a multiple of 16, as at QVGA's level 0): the stores are whole lines, written once. Rows [r0, znew)
@@ -735,8 +696,8 @@ __device__ __forceinline__ void tiled_splat(const SplatGeom &g, int rows_i, int 
                 // (round 5) only the box the tile's taps can have reached -- a rigid warp moves a 64 x 16 tile into about 66 x 18 cells of
                 // its 70 x 22 window --: what lies beyond it in the window holds zeros that nobody needs to write now (the
                 // watermarks say what is initialised; a later window, or the sweep after the last tile, takes care of the rest)
-                const int vreach = SF_SPLAT_BOX ? min(wv0 + WIN_V, uniform_i(win.vmax) + 1) : wv0 + WIN_V;
-                const int ureach = SF_SPLAT_BOX ? min(WIN_U, uniform_i(win.umax) + 1 - wu0) : WIN_U;
+                const int vreach = min(wv0 + WIN_V, uniform_i(win.vmax) + 1);
+                const int ureach = min(WIN_U, uniform_i(win.umax) + 1 - wu0);
                 const int vend = min(vreach, rows_i);
                 const int znew = min((vend + 15) & ~15, rows_i), r0 = wv0 & ~15;
                 const int ng = (znew - r0 + 15) >> 4;  // groups per column

@@ -45,9 +45,6 @@ __device__ __forceinline__ void run_stages(const KArgs &a, int b, int stage_mask
     long long t0 = 0, t1 = 0;
     long long *prof = a.state[b].prof;
     const bool writer = cl_writer(cs);
-#ifdef SF_NO_STAGE_TIMED
-#define STAGE_TIMED(slot, call) call
-#else
 #define STAGE_TIMED(slot, call)               \
     do {                                      \
         call;                                 \
@@ -57,7 +54,6 @@ __device__ __forceinline__ void run_stages(const KArgs &a, int b, int stage_mask
             t0 = t1;                          \
         }                                     \
     } while (0)
-#endif
     const long long t_begin = wall_clock64(), c_begin = clock64();
     t0 = t_begin;
     if ((stage_mask & (ST_PYR_OLD | ST_PYR_NEW)) == (ST_PYR_OLD | ST_PYR_NEW)) {

@@ -71,12 +71,6 @@ __device__ __noinline__ void kmc_collect_and_sum(LDS KmClShared &kc, LDS Cluster
     qlo = uniform_i(qlo);
     qhi = uniform_i(qhi);
     const int n_chunks = (qhi - qlo + SF_NT - 1) / SF_NT;
-#ifdef SF_KMC_FINE
-    long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tph = clock64();
-#define PH(i) do { if (tid == 0) { const long long n_ = clock64(); ph[i] += n_ - tph; tph = n_; } } while (0)
-#else
-#define PH(i) do {} while (0)
-#endif
         // ---- ordered sums of the clusters this workgroup owns (KMeans.cpp:215-221), in pixel order.
         // R chunks (a quad of consecutive pixels per thread and chunk) are loaded and ranked together; the members of the
         // owned clusters are then compacted into LDS and added GROUP by group, a group being as many consecutive chunks as fit
@@ -112,9 +106,7 @@ __device__ __noinline__ void kmc_collect_and_sum(LDS KmClShared &kc, LDS Cluster
                 }
                 if (lane < nown) kc.wcnt[c5][wave][lane] = cnt_lane;
             }
-            PH(0);
             __syncthreads();  // also: the previous group's sums have consumed kc.run
-            PH(1);
             // the depths of the quads: issued now, in flight during the offset arithmetic, consumed by the scatter
             vfloat4 dz4[R];
 #pragma unroll
@@ -147,7 +139,6 @@ __device__ __noinline__ void kmc_collect_and_sum(LDS KmClShared &kc, LDS Cluster
                     chunk_all[c5] += mem;
                 }
             }
-            PH(2);
             // groups of consecutive chunks whose members (all owned clusters together) fit the LDS runs
             int g0 = 0;
             while (g0 < R) {  // uniform: every lane derives the same group bounds from the same counts
@@ -226,9 +217,7 @@ __device__ __noinline__ void kmc_collect_and_sum(LDS KmClShared &kc, LDS Cluster
                 const int sum_c = (tid < 3 * nown) ? tid / 3 : 0;
                 const int sum_n = __builtin_amdgcn_ds_bpermute(sum_c << 2, grp_members);
                 const int sum_o = __builtin_amdgcn_ds_bpermute(sum_c << 2, run_start);
-                PH(3);
                 __syncthreads();
-                PH(4);
                 if (tid < 3 * nown) {  // strictly front to back per sum
                     const int r = tid - 3 * sum_c;
                     const LDS float *src = &kc.run[r][sum_o];
@@ -275,7 +264,6 @@ __device__ __noinline__ void kmc_collect_and_sum(LDS KmClShared &kc, LDS Cluster
                     for (; j < n; j++) acc += src[j];
                     total += n;
                 }
-                PH(5);
                 g0 = g1;
                 if (g0 < R) __syncthreads();  // the next group's scatter may overwrite the runs
             }
@@ -289,12 +277,6 @@ __device__ __noinline__ void kmc_collect_and_sum(LDS KmClShared &kc, LDS Cluster
             cs.in[4 * c + r] = __float_as_uint(acc);
             if (r == 0) cs.in[4 * c + 3] = (unsigned)total;
         }
-    PH(6);
-#ifdef SF_KMC_FINE
-    if (tid == 0 && prof_out)
-        for (int i = 0; i < 7; i++) prof_out[i] += ph[i];
-#endif
-#undef PH
 }
 
 __device__ __noinline__ void stage_kmeans_cluster(const KArgs &a, int b, LDS KmClusterShared &sh, LDS ClusterShared &cs, int tid) {

@@ -4,8 +4,7 @@
 // deterministic float operation sequences by something faster (and differently rounded) is put back, whatever it
 // costs, so that what remains between this build and the CPU restatement is only what the reference itself leaves
 // open (the internal order of its Eigen GEMM, FrontEnd.cpp:640-641) or delegates to a library (libm, Eigen's
-// eigensolver). profiles/PARITY.md has the table: this build against the oracle over the hunt seeds, then ONE product
-// shortcut switched back on at a time (the SF_RO_* switches below).
+// eigensolver). profiles/PARITY.md has the table: this build against the oracle over the hunt seeds.
 //
 //   what the reference does (its source fixes the order)                        product build          this build
 //   warp / 5-frame residual splat: float `+=` of float(w) * depth_w per target  exact Q26 / Q28        the taps of a cell
@@ -40,9 +39,6 @@
 //  product; larger levels keep the exact integer sums (sf_device_common.h). The per-cell source lists of the fall-back are
 //  scratch of the WORKGROUP that runs the warp (KArgs::ro_list: one block of 256 KB per stream or resident workgroup).
 // ---------------------------------------------------------------------------------------------
-#ifndef SF_ORDERED_COARSE_SPLAT
-#define SF_ORDERED_COARSE_SPLAT 1
-#endif
 #ifndef SF_ORDERED_SPLAT_MAX_PIXELS
 #define SF_ORDERED_SPLAT_MAX_PIXELS 2048  // (<= SF_CLUSTER_SOLO_PIXELS: a cluster's workgroups run such levels each on its own)
 #endif
@@ -313,14 +309,11 @@ template <class Src>
 __device__ __forceinline__ void ordered_splat(const KArgs &a, const SplatGeom &g, const LevelCoord &lc, int rows_i, int cols_i,
                                               const Src &src, gptr<long long> acc_d, gptr<long long> acc_i, gptr<int> list,
                                               LDS SplatWin &win, int tid, long long *fallbacks = nullptr) {
-#ifndef SF_ORDERED_TILE_SPLAT
-#define SF_ORDERED_TILE_SPLAT 1  // 0: always the lists (A/B and bisection builds)
-#endif
     // Both conditions go through readfirstlane: `rows_i` arrives in a VGPR (a member of KArgs read through a pointer the
     // compiler cannot prove uniform) and a branch on it is compiled as a DIVERGENT one -- EXEC masks around code that holds
     // barriers. That is how round 4's "address 0" fault came about (profiles/HISTORY.md, round 5; tools/diag/exec_lint.py): the
     // exit block of ro_splat's cell loop got a register copy IN FRONT of the `s_or_b64 exec` that re-enables its lanes.
-    if (SF_ORDERED_TILE_SPLAT && uniform_i(rows_i) <= SPLAT_TV) {
+    if (uniform_i(rows_i) <= SPLAT_TV) {
         if (uniform_i(ordered_tile_splat(g, lc, rows_i, cols_i, src, acc_d, acc_i, win, tid) ? 1 : 0)) return;
         if (tid == 0 && fallbacks) *fallbacks += 1;  // (a counter of the stream's profile: tests want to know that this path ran)
     }
@@ -328,41 +321,6 @@ __device__ __forceinline__ void ordered_splat(const KArgs &a, const SplatGeom &g
 }
 
 #if SF_REFORDER
-
-// ONE product shortcut back on at a time (attribution builds, tools/build_variant.sh):
-#ifndef SF_RO_SPLAT
-#define SF_RO_SPLAT 1   // 0: the product's exact integer splat sums (divided with IEEE division)
-#endif
-// ... or only at some levels of the pyramid: the ordered float splat runs at image levels [SF_RO_SPLAT_MIN_LEVEL, SF_RO_SPLAT_MAX_LEVEL]
-// (0 = full resolution), the product's integer sums (IEEE division) at the others -- which levels carry the sensitivity
-#ifndef SF_RO_SPLAT_MIN_LEVEL
-#define SF_RO_SPLAT_MIN_LEVEL 0
-#endif
-#ifndef SF_RO_SPLAT_MAX_LEVEL
-#define SF_RO_SPLAT_MAX_LEVEL 99
-#endif
-#define RO_SPLAT_AT(L) (SF_RO_SPLAT && (L) >= SF_RO_SPLAT_MIN_LEVEL && (L) <= SF_RO_SPLAT_MAX_LEVEL)
-#ifndef SF_RO_ROWS
-#define SF_RO_ROWS 1    // 0: the product's factored rows / three dot products (with SF_ROWS_FMA as given)
-#endif
-#ifndef SF_RO_P1_FP64
-#define SF_RO_P1_FP64 1 // 0: the product's fp32 lane sums, flushed into fp64 every SF_P1_FLUSH pixel pairs
-#endif
-#ifndef SF_RO_LABSUM
-#define SF_RO_LABSUM 1  // 0: the product's exact Q32.32 per-cluster sums
-#endif
-#ifndef SF_RO_JACOBI
-#define SF_RO_JACOBI 1  // 0: the product's round-robin Jacobi
-#endif
-#ifndef SF_RO_INIT_RES
-#define SF_RO_INIT_RES 1  // 0: the product's initial mean |res| from the linearisation's scaled sums
-#endif
-#ifndef SF_RO_BEHIND
-#define SF_RO_BEHIND 1  // 0: the product's rule for points warped behind the camera
-#endif
-#ifndef SF_RO_SEQ64
-#define SF_RO_SEQ64 1   // 0: the fp64 sums ([C1]: AtA / AtB, sum |res|, ||res||^2) as per-lane partial sums + a tree, not row by row
-#endif
 
 #define RO_CHUNK 1024    // pixels per trip of the ordered per-cluster sums
 
@@ -409,21 +367,9 @@ __device__ __forceinline__ void ro_label_walk(const LDS RoChunk &c, int m, int t
 
 #endif  // SF_REFORDER
 
-#if SF_REFORDER
-#define RO_SPLAT_AT_(L) RO_SPLAT_AT(L)
-#else
-#define RO_SPLAT_AT_(L) false
-#endif
-// does level L (n pixels) of this launch take the ordered float splat? G: workgroups that share the level right now
-__device__ __forceinline__ bool splat_ordered(int L, int n, int G) {
-#if SF_REFORDER
-    (void)n; (void)G;
-    return RO_SPLAT_AT_(L);
-#else
-    (void)L;
-    return SF_ORDERED_COARSE_SPLAT && G == 1 && n <= SF_ORDERED_SPLAT_MAX_PIXELS;
-#endif
-}
+// does a level of n pixels take the ordered float splat (the reference-order build: every level)? G: workgroups that share
+// the level right now
+__device__ __forceinline__ bool splat_ordered(int n, int G) { return SF_REFORDER || (G == 1 && n <= SF_ORDERED_SPLAT_MAX_PIXELS); }
 // the source lists this workgroup uses: the record slot's (reference-order build: every level, any size) or the workgroup's own block
 __device__ __forceinline__ gptr<int> ro_list_of(const KArgs &a, size_t rb, int b) {
 #if SF_REFORDER

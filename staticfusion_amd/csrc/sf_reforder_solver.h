@@ -9,11 +9,7 @@
 //  one pixel of validPixels: its two Jacobian rows (reference FrontEnd.cpp:544-585)
 // ---------------------------------------------------------------------------------------------
 struct RoPixel {
-#if SF_RO_ROWS
     float ac[6], bc, ad[6], bd;  // A(cont, 0..5), B(cont) of the colour row and of the geometry row
-#else
-    PixFact<float> p;            // the product's factored form
-#endif
 };
 
 struct RoRec {
@@ -42,15 +38,11 @@ __device__ __forceinline__ void ro_load(const RoPlanes &pl, int idx, RoRec &r) {
     r.ddu = gld(pl.p[R_DDU], idx);
     r.ddv = gld(pl.p[R_DDV], idx);
     r.lab = (int)gld(pl.lab, idx);
-#if !SF_RO_BEHIND
-    r.dw = fabsf(r.dw);  // the product's records carry validPixels in the sign
-#endif
 }
 
 __device__ __forceinline__ void ro_pixel(const LevelGeom &g, int idx, const RoRec &r, RoPixel &o) {
     float fu, fv;
     split_index(g, idx, fu, fv);
-#if SF_RO_ROWS
     // Inter coordinates (calculateCoord, :402-404) from the pyramid's and the warp's xx / yy (:385-386, :874-880; on the
     // Warped := Pred iteration the warped coordinates are the prediction pyramid's, :1107-1108)
     const float xn = (g.inv_f_pyr * (fu - g.disp_u_i)) * r.dn, yn = (g.inv_f_pyr * (fv - g.disp_v_i)) * r.dn;
@@ -92,14 +84,10 @@ __device__ __forceinline__ void ro_pixel(const LevelGeom &g, int idx, const RoRe
         o.ad[5] = tw * (dycomp * y - dzcomp * x);
         o.bd = tw * (-ddt_);
     }
-#else
-    fact_from_record<float>(g, fu, fv, r.dn, r.dw, r.dcu, r.dcv, r.dct, r.ddu, r.ddv, o.p);
-#endif
 }
 
 // res = -B; res += Var(k) * A.col(k), k = 0..5 (:644-646), for both rows of the pixel
 __device__ __forceinline__ void ro_residuals(const RoPixel &o, const float (&V)[6], float &res_c, float &res_d) {
-#if SF_RO_ROWS
     res_c = -o.bc;
     res_d = -o.bd;
 #pragma unroll
@@ -107,22 +95,13 @@ __device__ __forceinline__ void ro_residuals(const RoPixel &o, const float (&V)[
         res_c += V[k] * o.ac[k];
         res_d += V[k] * o.ad[k];
     }
-#else
-    fact_residuals<float>(o.p, V, res_c, res_d);
-#endif
 }
 __device__ __forceinline__ void ro_abs_b(const RoPixel &o, float &abs_c, float &abs_d) {
-#if SF_RO_ROWS
     abs_c = fabsf(-o.bc);
     abs_d = fabsf(-o.bd);
-#else
-    abs_c = fabsf(o.p.bct);
-    abs_d = fabsf(o.p.bdt);
-#endif
 }
 // Aw = res_weight * A, Bw = res_weight * B of both rows (:627-636): aw[0..5] the row, aw[6] its right-hand side
 __device__ __forceinline__ void ro_weighted_rows(const RoPixel &o, float w_c, float w_d, float (&awc)[7], float (&awd)[7]) {
-#if SF_RO_ROWS
 #pragma unroll
     for (int k = 0; k < 6; k++) {
         awc[k] = w_c * o.ac[k];
@@ -130,29 +109,6 @@ __device__ __forceinline__ void ro_weighted_rows(const RoPixel &o, float w_c, fl
     }
     awc[6] = w_c * o.bc;
     awd[6] = w_d * o.bd;
-#else
-    const PixFact<float> &p = o.p;
-    {
-        const float P = w_c * p.pc, Q = w_c * p.qc;
-        awc[0] = -P;
-        awc[1] = -Q;
-        awc[2] = vfma(P, p.xd, Q * p.yd);
-        awc[3] = vfma(P, p.xyd, Q * p.yyd);
-        awc[4] = -vfma(P, p.xxd, Q * p.xyd);
-        awc[5] = vfma(P, p.y, -(Q * p.x));
-        awc[6] = -(w_c * p.bct);
-    }
-    {
-        const float W = w_d * p.twd, Pd = w_d * p.pd, Qd = w_d * p.qd;
-        awd[0] = -Pd;
-        awd[1] = -Qd;
-        awd[2] = vfma(Pd, p.xd, vfma(Qd, p.yd, W));
-        awd[3] = vfma(Pd, p.xyd, vfma(Qd, p.yyd, W * p.y));
-        awd[4] = -vfma(Pd, p.xxd, vfma(Qd, p.xyd, W * p.x));
-        awd[5] = vfma(Pd, p.y, -(Qd * p.x));
-        awd[6] = -(w_d * p.bdt);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -168,9 +124,6 @@ __device__ __noinline__ void ro_seg_prior(const KArgs &a, int b, int L, LDS Solv
     const auto labp = as_global((const uint8_t *)a.labels + sb);
     const auto vlab = as_global((const uint8_t *)a.rec_lab + rb);
     RoLabelAcc la{0.f, 0, 0, 0};
-#if !SF_RO_LABSUM
-    if (tid < SF_NC) s.prior_sum[tid] = 0;
-#endif
     __syncthreads();
     for (int base = 0; base < n; base += RO_CHUNK) {
         for (int q = tid; q < RO_CHUNK; q += SF_NT) {
@@ -182,16 +135,10 @@ __device__ __noinline__ void ro_seg_prior(const KArgs &a, int b, int L, LDS Solv
                 if (l != SF_NC) {  // labels_ref(v, u) != NUM_CLUSTERS
                     lab = l;
                     const float dn = gld(dnew, idx);
-                    float dw = gld(dwp, idx);
-#if !SF_RO_BEHIND
-                    dw = fabsf(dw);
-#endif
+                    const float dw = gld(dwp, idx);
                     if (dn != 0.f && dw != 0.f) {  // Null(v, u) == 0
                         flag |= 1;
                         val = 1.f - kz * fabsf(dn - dw);
-#if !SF_RO_LABSUM
-                        lds_add(&s.prior_sum[l], to_fix(val, FIX_RES, 1.0e6f));
-#endif
                     }
                     if ((int)gld(vlab, idx) != SF_INVALID_LABEL) flag |= 2;
                 }
@@ -215,12 +162,7 @@ __device__ __noinline__ void ro_seg_prior(const KArgs &a, int b, int L, LDS Solv
                 bp = -1.f;
             } else {
                 lt = ratio;
-#if SF_RO_LABSUM
-                const float sum = la.sum;
-#else
-                const float sum = (float)((double)s.prior_sum[l] * (1.0 / 4294967296.0));
-#endif
-                bp = std_max(-1.f, std_min(2.f, sum / la.n_val));
+                bp = std_max(-1.f, std_min(2.f, la.sum / la.n_val));
             }
         }
         s.b_prior[l] = bp;
@@ -237,7 +179,6 @@ __device__ __noinline__ void ro_initial_residual(const KArgs &a, int b, int L, L
     const RoPlanes pl = ro_planes(a, b, L, s);
     const int lane = tid & 63, wave = tid >> 6;
     double t = 0.0;
-#if SF_RO_SEQ64
     for (int base = c.begin; base < c.n; base += RO_CHUNK) {
         for (int q = tid; q < RO_CHUNK; q += SF_NT) {
             const int idx = base + q;
@@ -268,19 +209,6 @@ __device__ __noinline__ void ro_initial_residual(const KArgs &a, int b, int L, L
         }
         __syncthreads();
     }
-#else
-    for (int idx = c.begin + tid; idx < c.n; idx += SF_NT) {
-        RoRec r;
-        ro_load(pl, idx, r);
-        if (r.lab == SF_INVALID_LABEL) continue;
-        RoPixel px;
-        ro_pixel(c.g, idx, r, px);
-        float ac, ad;
-        ro_abs_b(px, ac, ad);
-        t += (double)ac;
-        t += (double)ad;
-    }
-#endif
     t = wave_sum_f64(t);  // (row-by-row sums: lane 0 of wave 0 holds the sum, every other lane 0.0)
     if (lane == 0) s.red[wave][0] = t;
     __syncthreads();
@@ -303,7 +231,6 @@ __device__ __noinline__ void ro_pass1(const KArgs &a, int b, int L, LDS SolveSha
     float Vr[6];
 #pragma unroll
     for (int q = 0; q < 6; q++) Vr[q] = uniform_f(s.Var[q]);
-#if SF_RO_SEQ64 && SF_RO_P1_FP64
     // AtA / AtB row by row ([C1]): the weighted rows of a chunk of pixels go to LDS, lane q < 27 owns sum q and adds the products
     // of the colour row, then of the depth row, pixel after pixel
     int ei = 0, ej = 6;  // the two row entries whose product this lane sums (21 + i: entry i times Bw)
@@ -357,66 +284,6 @@ __device__ __noinline__ void ro_pass1(const KArgs &a, int b, int L, LDS SolveSha
     if (lane < 27) s.red[wave][lane] = wave == 0 ? sum : 0.0;
 }
 
-#else
-    double acc[27];
-#pragma unroll
-    for (int q = 0; q < 27; q++) acc[q] = 0.0;
-#if !SF_RO_P1_FP64
-    float acc32[27];
-#pragma unroll
-    for (int q = 0; q < 27; q++) acc32[q] = 0.f;
-    int since = 0;
-#endif
-    for (int idx = c.begin + tid; idx < c.n; idx += SF_NT) {
-        RoRec r;
-        ro_load(pl, idx, r);
-        if (r.lab == SF_INVALID_LABEL) continue;
-        RoPixel px;
-        ro_pixel(c.g, idx, r, px);
-        float res_c, res_d;
-        ro_residuals(px, Vr, res_c, res_d);  // the residuals of the previous iteration's solution (-B for the first)
-        const float b_weight = std_max(0.f, std_min(1.f, s.b_segm[r.lab]));
-        const float w_c = b_weight * vrsq(1.f + sqf(res_c * inv_c_Cauchy));
-        const float w_d = b_weight * vrsq(1.f + sqf(res_d * inv_c_Cauchy));
-        float awc[7], awd[7];
-        ro_weighted_rows(px, w_c, w_d, awc, awd);
-#if SF_RO_P1_FP64
-#pragma unroll
-        for (int row = 0; row < 2; row++) {
-            const float(&aw)[7] = row ? awd : awc;
-            int q = 0;
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int j = i; j < 6; j++) acc[q++] += (double)aw[i] * (double)aw[j];
-#pragma unroll
-            for (int i = 0; i < 6; i++) acc[21 + i] += (double)aw[i] * (double)aw[6];
-        }
-#else
-        accum_row(acc32, awc);
-        accum_row(acc32, awd);
-        if (++since == 2 * SF_P1_FLUSH) {  // a lane's fp32 sums hold as many terms as the product's (pixel pairs there)
-            since = 0;
-#pragma unroll
-            for (int q = 0; q < 27; q++) {
-                acc[q] += (double)acc32[q];
-                acc32[q] = 0.f;
-            }
-        }
-#endif
-    }
-#if !SF_RO_P1_FP64
-#pragma unroll
-    for (int q = 0; q < 27; q++) acc[q] += (double)acc32[q];
-#endif
-#pragma unroll
-    for (int q = 0; q < 27; q++) {
-        const double t = wave_sum_f64(acc[q]);
-        if (lane == 0) s.red[wave][q] = t;
-    }
-}
-#endif  // SF_RO_SEQ64 && SF_RO_P1_FP64
-
 // ---------------------------------------------------------------------------------------------
 //  pass 2: residuals with the new solution, per-cluster sums of |res_c| + |res_d| in validPixels order, ||res||^2
 //  (:644-667, :689)
@@ -430,7 +297,6 @@ __device__ __noinline__ void ro_pass2(const KArgs &a, int b, int L, LDS SolveSha
     for (int q = 0; q < 6; q++) Vr[q] = uniform_f(s.Var[q]);
     double sq = 0.0;
     RoLabelAcc la{0.f, 0, 0, 0};
-    (void)la;
     for (int base = c.begin; base < c.n; base += RO_CHUNK) {
         for (int q = tid; q < RO_CHUNK; q += SF_NT) {
             const int idx = base + q;
@@ -444,18 +310,10 @@ __device__ __noinline__ void ro_pass2(const KArgs &a, int b, int L, LDS SolveSha
                     ro_pixel(c.g, idx, r, px);
                     float res_c, res_d;
                     ro_residuals(px, Vr, res_c, res_d);
-#if SF_RO_SEQ64
                     s.ro2.rc[q] = res_c;
                     s.ro2.rd[q] = res_d;
-#else
-                    sq += (double)res_c * (double)res_c;
-                    sq += (double)res_d * (double)res_d;
-#endif
                     val = fabsf(res_c) + fabsf(res_d);
                     lab = r.lab;
-#if !SF_RO_LABSUM
-                    lds_add(&s.lab_sum[lab], (long long)to_fix32_pos(val));
-#endif
                 }
             }
             s.ro.val[q] = val;
@@ -463,10 +321,7 @@ __device__ __noinline__ void ro_pass2(const KArgs &a, int b, int L, LDS SolveSha
             s.ro.flag[q] = 1;
         }
         __syncthreads();
-#if SF_RO_LABSUM
         ro_label_walk(s.ro, min(RO_CHUNK, c.n - base), tid, la);
-#endif
-#if SF_RO_SEQ64
         if (tid == SF_NC) {  // res.squaredNorm(): row after row ([C1]), on the lane next to the 24 of the per-cluster sums
             const int m = min(RO_CHUNK, c.n - base);
             for (int q = 0; q < m; q++) {
@@ -475,12 +330,9 @@ __device__ __noinline__ void ro_pass2(const KArgs &a, int b, int L, LDS SolveSha
                 sq += (double)s.ro2.rd[q] * (double)s.ro2.rd[q];
             }
         }
-#endif
         __syncthreads();
     }
-#if SF_RO_LABSUM
     if (tid < SF_NC) s.aver_res_label[tid] = la.sum;
-#endif
     sq = wave_sum_f64(sq);  // (row-by-row: one lane holds the sum, every other lane 0.0)
     if (lane == 0) s.red[wave][27] = sq;
 }

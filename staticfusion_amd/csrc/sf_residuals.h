@@ -61,7 +61,7 @@ __device__ __noinline__ void stage_residuals(const KArgs &a, int b, int index, b
         s.lab_sum[tid] = 0;
         s.lab_cnt[tid] = 0;
     }
-    const bool ordered = uniform_i(splat_ordered(0, n, G) ? 1 : 0) != 0;  // full resolution: the reference-order build, or an image of at most 2048 pixels
+    const bool ordered = uniform_i(splat_ordered(n, G) ? 1 : 0) != 0;  // full resolution: the reference-order build, or an image of at most 2048 pixels
     const bool lazy = ordered || uniform_i(splat_lazy_ok(rows, cols, G) ? 1 : 0) != 0;  // see solve_warp
     if (!lazy)
     for (int idx = tid + rank * SF_NT; idx < n; idx += SF_NT * G) {  // agent-scope stores: see solve_warp
@@ -130,17 +130,11 @@ __device__ __noinline__ void stage_residuals(const KArgs &a, int b, int index, b
                     }
                     if (si != 0 && dc != 0.f) {
                         float dw, iw;
-                        if (ordered)
-                            ro_unpack_cell(sd, dw, iw);
-                        else
-                            normalise_acc(sd, si, dw, iw);
+                        ro_unpack_cell(sd, dw, iw);  // (every level of this build takes the ordered splat)
                         if (dw != 0.f && lb < SF_NC) {
                             const float idiff = (db != 0.f) ? ic : 0.f;  // intensity_diff (:937,1022)
                             val = fabsf(dc - dw) + kph_ro * fabsf(idiff - iw);
                             lab = lb;
-#if !SF_RO_LABSUM
-                            lds_add(&s.lab_sum[lab], to_fix(val, FIX_RES, 1.0e6f));
-#endif
                         }
                     }
                 }
@@ -153,12 +147,7 @@ __device__ __noinline__ void stage_residuals(const KArgs &a, int b, int index, b
             __syncthreads();
         }
         if (tid < SF_NC && commit_ok(cs)) {
-#if SF_RO_LABSUM
-            const float sum = la.sum;
-#else
-            const float sum = (float)((double)s.lab_sum[tid] * (1.0 / 4294967296.0));
-#endif
-            st.cluster_res[tid] = (la.n_val > 0) ? sum / float(2 * (la.n_val + 1)) : __int_as_float(0x7fc00000);
+            st.cluster_res[tid] = (la.n_val > 0) ? la.sum / float(2 * (la.n_val + 1)) : __int_as_float(0x7fc00000);
         }
         cluster_barrier(cs, tid);
         return;

@@ -24,22 +24,13 @@
 #include "sf_device_common.h"
 #include "sf_smallmath.h"
 // the linearisation walks register strips in the one-workgroup builds (solve_linearise_strips) and LDS tiles in a cluster,
-// whose workgroups share a level tile by tile (solve_linearise); -DSF_LIN_STRIPS=0: tiles everywhere (A/B)
-#ifndef SF_LIN_STRIPS
+// whose workgroups share a level tile by tile (solve_linearise)
 #ifdef SF_CLUSTER
 #define SF_LIN_STRIPS 0
 #else
 #define SF_LIN_STRIPS 1
 #endif
-#endif
-#if SF_REFORDER && SF_RO_BEHIND
-#define LS_RO_BEHIND 1  // validPixels by the reference's rule (:415-427), carried by the label plane
-#else
-#define LS_RO_BEHIND 0
-#endif
-#ifndef LS_ROWS
 #define LS_ROWS 62  // rows a wave owns in a strip (lanes 1 .. LS_ROWS; lane 0 and lane LS_ROWS + 1 hold the halo rows)
-#endif
 #define TILE_V 64
 #define TILE_U (2 * SF_NT / TILE_V)  // two centre pixels per lane
 #define TILE_LV (TILE_V + 2)
@@ -74,9 +65,7 @@ struct LinTile {  // linearisation tile (with halo)
 // the group leaders of a wave touch consecutive 8-byte words). A lane's fp32 partial sum then never holds more than
 // 4 SF_P1_FLUSH terms: the rounding error of the accumulated AtA / AtB drops about tenfold against one fp32 sum over the
 // lane's whole share (<= 600 terms at QVGA), which is what moved b by 4e-5 against the oracle's fp64 sums ([C1]).
-#ifndef SF_P1_FLUSH
 #define SF_P1_FLUSH 32
-#endif
 #define P1_GROUP (SF_NT == 256 ? 4 : 16)  // 1024-thread builds: a lane sums a quarter of the terms, rows of 16 lanes share a set
 #define P1_SETS (SF_NT / P1_GROUP)
 #define P1_SETS_PER_WAVE (64 / P1_GROUP)
@@ -261,7 +250,7 @@ __device__ __noinline__ void solve_warp(const KArgs &a, int b, int L, LDS SolveS
     // agent-scope atomics and atomic loads after this, so the two hand-overs below need no fence (sf_cluster.h)
     // coarse levels (and every level of the reference-order build): the reference's float sums in the reference's order
     // (uniform by construction, made so for the compiler: branches around barriers must be scalar branches, see ordered_splat)
-    const bool ordered = uniform_i(splat_ordered(L, n, G) ? 1 : 0) != 0;
+    const bool ordered = uniform_i(splat_ordered(n, G) ? 1 : 0) != 0;
     const bool lazy = ordered || uniform_i(splat_lazy_ok(rows_i, cols_i, G) ? 1 : 0) != 0;  // one workgroup: the splat zeroes / initialises the cells itself
     if (!lazy)
     for (int idx = tid + rank * SF_NT; idx < n; idx += SF_NT * G) {
@@ -396,7 +385,7 @@ __device__ __noinline__ void solve_linearise(const KArgs &a, int b, int L, bool 
     const auto rec_lab = as_global(a.rec_lab + rb);
     const bool seg = a.p.segmentation_enabled != 0;
     const bool dbg = a.p.debug_planes != 0;
-    const bool ordered = splat_ordered(L, a.ln[L], G);  // what solve_warp left in the accumulator cells of this level
+    const bool ordered = splat_ordered(a.ln[L], G);  // what solve_warp left in the accumulator cells of this level
     if (tid == 0) s.first = first ? 1 : 0;
 
     const float f = float(cols_i) / (2.f * a.tan_half_fovh);
@@ -506,7 +495,7 @@ __device__ __noinline__ void solve_linearise(const KArgs &a, int b, int L, bool 
                 // image gives a negative warped depth, which the reference keeps in validPixels (:816-823 has no depth test);
                 // here such a pixel is left out everywhere (counts, sums, passes), because the sign of the stored warped
                 // depth is what marks membership for the passes. It needs a diverged pose to happen at all.
-#if SF_REFORDER && SF_RO_BEHIND
+#if SF_REFORDER
                 valid = !nul && (u != 0) && (v != 0) && (u != cols_i - 1) && (v != rows_i - 1);  // the reference's rule, :415-427
 #else
                 valid = !nul && (dw > 0.f) && (u != 0) && (v != 0) && (u != cols_i - 1) && (v != rows_i - 1);
@@ -542,7 +531,7 @@ __device__ __noinline__ void solve_linearise(const KArgs &a, int b, int L, bool 
                 // (a point behind the camera that still projects into the image: a diverged pose) stays negative = not valid;
                 // the segmentation prior then sees its magnitude (solve_seg_prior), the one place where this differs from the
                 // reference, which carries such a pixel through with its sign
-#if SF_REFORDER && SF_RO_BEHIND
+#if SF_REFORDER
                 gst(rec[R_DW], idx, dw);  // validPixels rides in the label plane of this build, the sign is the warp's
 #else
                 gst(rec[R_DW], idx, valid ? dw : -fabsf(dw));
@@ -603,9 +592,7 @@ __device__ __noinline__ void solve_linearise(const KArgs &a, int b, int L, bool 
 // ---------------------------------------------------------------------------------------------
 // computeSegPrior rides in the sweep (the product builds: its sums are integers, whoever adds them): the pass of its own read
 // 9 bytes per pixel again -- 2.7 % of the full solver's HBM traffic. The reference-order build keeps ro_seg_prior.
-#ifndef SF_LIN_FUSED_PRIOR
 #define SF_LIN_FUSED_PRIOR (SF_LIN_STRIPS && !SF_REFORDER)
-#endif
 __device__ __forceinline__ void seg_prior_begin(LDS SolveShared &s, int tid);
 __device__ __forceinline__ void seg_prior_finish(LDS SolveShared &s, LDS ClusterShared &cs, int tid);
 #if SF_LIN_STRIPS
@@ -628,7 +615,7 @@ __device__ __noinline__ void solve_linearise_strips(const KArgs &a, int b, int L
     const auto rec_lab = as_global(a.rec_lab + rb);
     constexpr bool seg = SEG;  // (a template parameter like the two others: no label load, no prior sums without segmentation)
     constexpr bool dbg = DBG;
-    const bool ordered = uniform_i(splat_ordered(L, a.ln[L], 1) ? 1 : 0) != 0;  // what solve_warp left in the accumulator cells of this level
+    const bool ordered = uniform_i(splat_ordered(a.ln[L], 1) ? 1 : 0) != 0;  // what solve_warp left in the accumulator cells of this level
     if (tid == 0) s.first = first ? 1 : 0;
     constexpr bool fuse_prior = SF_LIN_FUSED_PRIOR && seg;
     if (fuse_prior) seg_prior_begin(s, tid);  // (uniform; a barrier)
@@ -760,7 +747,7 @@ __device__ __noinline__ void solve_linearise_strips(const KArgs &a, int b, int L
             const float ddt_ = dn - dw;                                                                             \
             const int lab = seg ? (wN[sc] >> 8) : ((dn != 0.f) ? 0 : SF_NC);                                        \
             /* validPixels (reference :415-427), with the product's rule for points behind the camera (solve_linearise) */\
-            const bool valid = v_inner && !nul && (LS_RO_BEHIND || dw > 0.f) && (u != 0) && (u != cols_i - 1);      \
+            const bool valid = v_inner && !nul && (SF_REFORDER || dw > 0.f) && (u != 0) && (u != cols_i - 1);       \
             float dcu_ = 0.f, dcv_ = 0.f, ddu_ = 0.f, ddv_ = 0.f;                                                   \
             if (valid) {  /* (an inner pixel: all four neighbours are inside the image) */                          \
                 const float D_l = wD[sl], I_l = wI[sl], D_r = wD[sr], I_r = wI[sr];                                 \
@@ -803,8 +790,8 @@ __device__ __noinline__ void solve_linearise_strips(const KArgs &a, int b, int L
                 }                                                                                                   \
                 pr_valid += valid ? 1 : 0;                                                                          \
             }                                                                                                       \
-            /* the SIGN carries validPixels (solve_linearise); LS_RO_BEHIND: the label plane does, the sign is the warp's */\
-            gst(rec[R_DW], idx, (LS_RO_BEHIND || valid) ? dw : -fabsf(dw));                                         \
+            /* the SIGN carries validPixels (solve_linearise); SF_REFORDER: the label plane does, the sign is the warp's */\
+            gst(rec[R_DW], idx, (SF_REFORDER || valid) ? dw : -fabsf(dw));                                          \
             gst(rec[R_DCU], idx, dcu_);                                                                             \
             gst(rec[R_DCV], idx, dcv_);                                                                             \
             gst(rec[R_DCT], idx, (valid || dbg) ? dct_ : 0.f);  /* 0 outside validPixels: the passes run branch-free over every pixel */\
@@ -979,19 +966,12 @@ __device__ __noinline__ void solve_seg_prior(const KArgs &a, int b, int L, LDS S
 __device__ __noinline__ void solve_filter_and_update(const KArgs &a, LDS SolveShared &s, int level, int lane) {
     // est_cov = AtA.inverse() * res.squaredNorm()
     LDS double *Ad = s.dwork, *V = s.dwork + 72;
-#ifdef SF_FILTER_PROFILE
-    long long ft = wall_clock64();
-#define FILTER_MARK(slot) do { if (lane == 0) { const long long n_ = wall_clock64(); s.prof[slot] += n_ - ft; ft = n_; } } while (0)
-#else
-#define FILTER_MARK(slot) do {} while (0)
-#endif
     {
         double aa = (lane < 36) ? (double)s.AtA[lane] : 0.0, ainv;
         inverse6_lanes(aa, ainv, lane);
         if (lane < 36) s.est_cov[lane] = (float)ainv * s.res_sqnorm;
     }
     __builtin_amdgcn_wave_barrier();
-    FILTER_MARK(21);
 
     float twist[6];
     for (int i = 0; i < 6; i++) twist[i] = s.Var[i];
@@ -1009,7 +989,7 @@ __device__ __noinline__ void solve_filter_and_update(const KArgs &a, LDS SolveSh
         {
             const int l = (lane < 36) ? lane : 0, i = l / 6, j = l - 6 * i;
             double sa = (double)s.est_cov[(i >= j) ? i * 6 + j : j * 6 + i], vv;  // the lower triangle, mirrored
-#if SF_REFORDER && SF_RO_JACOBI
+#if SF_REFORDER
             if (lane < 36) S[lane] = sa;
             __builtin_amdgcn_wave_barrier();
             jacobi_eig6_wave(S, V, lane);  // the cyclic order of the oracle ([C5]), element for element
@@ -1023,7 +1003,6 @@ __device__ __noinline__ void solve_filter_and_update(const KArgs &a, LDS SolveSh
 #endif
         }
         __builtin_amdgcn_wave_barrier();
-        FILTER_MARK(22);
         if (lane != 0) return;
         float kai_loc_sub[6], lt[6];
         log_twist_cm(s.T, lt);
@@ -1060,7 +1039,6 @@ __device__ __noinline__ void solve_filter_and_update(const KArgs &a, LDS SolveSh
     float tw[6];
     log_twist_cm(s.T, tw);
     for (int i = 0; i < 6; i++) s.twist[i] = tw[i];
-    FILTER_MARK(23);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1083,9 +1061,7 @@ __device__ __forceinline__ float vabs(float x) { return fabsf(x); }
 #endif
 // pass 1 folds each row's pre-weight into its Cauchy weight (one reciprocal square root per row instead of two): part of the
 // product build's arithmetic, off in the `precise` build, which keeps the reference's two-step association
-#ifndef SF_P1_FOLD
 #define SF_P1_FOLD (SF_FAST_WEIGHTS && SF_ROWS_FMA)
-#endif
 #if SF_ROWS_FMA
 __device__ __forceinline__ float vfma(float a, float b, float c) { return fmaf(a, b, c); }
 #else
@@ -1563,7 +1539,7 @@ __device__ __noinline__ void irls_seg_factor(const KArgs &a, LDS SolveShared &s,
 // wave 0, after pass 2: averages, solveSegmIteration, convergence test (reference :666-683)
 __device__ __noinline__ void irls_iteration_tail(const KArgs &a, LDS SolveShared &s, int N, int k, int lane) {
     const bool seg = a.p.segmentation_enabled != 0;
-#if !(SF_REFORDER && SF_RO_LABSUM)  // (the reference-order build's pass 2 leaves the sequential float sums there itself)
+#if !SF_REFORDER  // (the reference-order build's pass 2 leaves the sequential float sums there itself)
     if (lane < SF_NC) s.aver_res_label[lane] = (float)((double)s.lab_sum[lane] * (1.0 / 4294967296.0));
 #endif
     __builtin_amdgcn_wave_barrier();
@@ -1661,7 +1637,7 @@ __device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level,
 
     // initial aver_res = mean |res| with res = -B (reference :588-590). B = (pre-weight / max) * derivative:
     // the sums of raw pre-weight x |dct|, |ddt| come from the linearisation, so no extra pass over the records
-#if SF_REFORDER && SF_RO_INIT_RES
+#if SF_REFORDER
     ro_initial_residual(a, b, L, s, tid);  // from the rows' B, as the reference does
 #else
     if (tid == 0) {
@@ -1865,9 +1841,6 @@ __device__ __noinline__ void stage_solve(const KArgs &a, int b, LDS SolveShared 
         }
         if (tid < 36) st.est_cov[tid] = s.est_cov[tid];
         if (tid >= PF_WARP && tid <= PF_FILTER) st.prof[tid] += s.prof[tid];
-#ifdef SF_FILTER_PROFILE
-        if (tid >= 21 && tid <= 23) st.prof[tid] += s.prof[tid];
-#endif
         if (tid < SF_NC) {
             st.b_segm[tid] = s.b_segm[tid];
             st.b_prior[tid] = s.b_prior[tid];
@@ -1905,7 +1878,7 @@ __device__ __forceinline__ void debug_rows(const KArgs &a, int b, float *out, in
     const float *dnew = pyr_level(a, b, 0, 0, L);
     for (int idx = gtid; idx < n; idx += gstride) {
         const float dw = a.rec[R_DW][rb + idx];
-#if SF_REFORDER && SF_RO_BEHIND
+#if SF_REFORDER
         const bool in_valid = a.rec_lab[rb + idx] != SF_INVALID_LABEL;  // (this build's records keep the warp's own sign)
 #else
         const bool in_valid = dw > 0.f;

@@ -1,6 +1,6 @@
 """Attribution hunt: the SAME random eight-frame sequences (tests/sequence_cases.py) through SEVERAL builds of the library
-against the oracle, one summary per build -- which of the product's arithmetic shortcuts buys which share of the
-excursions (profiles/PARITY.md, round 4).
+against the oracle, one summary per build -- how the excursions differ between builds of different arithmetic, e.g. the
+product, precise and reference-order libraries (tools/final_measure.sh; round 4's attribution in profiles/PARITY.md).
 
     python tools/diag/attribution_hunt.py --first 8000 --count 600 --size 640x480 \
         --libs reforder=staticfusion_amd/csrc/libsf_hip_reforder.so,product=staticfusion_amd/csrc/libsf_hip.so \
