@@ -1,6 +1,8 @@
 """Exact (fp64) references of the warp splat, the IRLS normal equations, the 6 x 6 solve, the velocity filter and the SE(3)
 update -- each recomputed from the inputs the implementation under test gave that stage, and each returned together with the
-rounding bound a correct float implementation must meet (tests/test_exact_references.py).
+rounding bound a correct float implementation must meet (tests/test_exact_references.py) -- and, section D, of the stages
+between the warp and the rows: calculateCoord, the gradients, the pre-weights, the Jacobian rows and the segmentation prior
+(tests/test_exact_linearisation.py).
 
 Plain NumPy. Nothing here imports oracle/ or the product: the point is an answer that neither of them wrote.
 
@@ -363,3 +365,226 @@ def label_means(res_abs_pair, labels, n_labels=24):
     s = np.bincount(labels, weights=res_abs_pair, minlength=n_labels)[:n_labels]
     n = np.bincount(labels, minlength=n_labels)[:n_labels]
     return s / (2.0 * (n + 1)), n
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+#  D. linearisation and segmentation prior: calculateCoord, calculateDerivatives, computeWeights, the Jacobian rows
+#     (reference FrontEnd.cpp:393-586) and computeSegPrior (SegmentationBackground.cpp:53-103)
+# --------------------------------------------------------------------------------------------------------------------------
+# Every constant below is a count of float roundings (u = 2^-24 each; a 1-ulp hardware rcp / rsq counts 2 u, because
+# ulp(x) <= 2 u |x|), applied to the magnitude of the terms that can cancel. Products of two u-sized errors are covered by
+# the factor SECOND_ORDER. The float constants are the float32 values the code uses.
+EPS_INTENSITY = float(np.float32(1e-6))   # epsilon_intensity (:445)
+EPS_DEPTH = float(np.float32(0.005))      # epsilon_depth (:446)
+ERR_M_C, ERR_M_D = 1.0, float(np.float32(0.01))  # error_m_c, error_m_d (:491-492)
+K_DUVT_C, K_DUVT_D = 10.0, 200.0          # kduvt_c, kduvt_d (:487-488)
+SECOND_ORDER = 1.0 + 1e-5
+
+# gradient (rl D_r + rc D_l) / (rc + rl), r = |D| + eps:  D = a - b: u;  r: u |D| + u r <= 2 u r;  product r D: 2 + 1 + 1 = 4 u;
+# numerator: 4 u of each product + u of the sum <= 5 u (|t1| + |t2|);  denominator: 2 u of each r + u = 3 u;  so the quotient is
+# off by (5 + 3) u m, m = (|t1| + |t2|) / (rc + rl), plus its own rounding, 1/2 ulp of the value.
+C_GRADIENT = 8.0
+# raw pre-weight sqrtf(1.f / (e_m + k (|t| + |u| + |v|))), IEEE: two sums and the product 3 u, e_m + ...: u -> argument 4 u (all
+# terms positive); 1 / x: + u = 5 u; sqrt halves it and rounds: 2.5 + 1 = 3.5 u.
+C_WEIGHT_RAW = 3.5
+# normalised: the maximum is one of the raw values (3.5 u), 1.f / max: + u = 4.5 u, times the raw value (3.5 u), rounded (u): 9 u
+C_WEIGHT = 9.0
+# The product's kernels (fact_from_record + debug_rows of sf_solver.h), from the stored derivative planes:
+#   pre-weight  twc = (inv_max_c rsq(1 + e)) kph:  argument 4 u -> 2 u, rsq 1 ulp = 2 u, inv_max_c 4.5 u (above: its minimum-e
+#               argument 4 u, 1 / x u, sqrt -> 3.5 u, 1 / max u), two products 2 u                                       = 10.5 u
+#               (twd = inv_max_d rsq(0.01 + e): one product less, 9.5 u)
+#   fd = f rcp(d):  f = float(cols) / (2 tan): tan of another libm 1 ulp = 2 u, the division u = 3 u; d = 0.5 (dn + dw) u,
+#               rcp 1 ulp = 2 u; the product u                                                                         = 7 u
+#   pc = twc (dcu fd): two products                                                                          10.5 + 7 + 2 = 19.5 u
+#   geometry    x = 0.5 (xn + xw): xn = (inv_f_pyr (u - disp)) dn: inv_f_pyr 3 u, two products = 5 u; xw = (u - disp) dw inv_f_w:
+#               inv_f_w = 1 / f 4 u, two products = 6 u; the sum u -> 7 u.  xd = x rcp(d): 7 + 3 + 1 = 11 u;  xyd = xd y: 11 + 7
+#               + 1 = 19 u;  xxd = fma(xd, x, d): 11 + 7 = 18 u on x^2 / d, u on d, the fma's rounding u <= 19 u
+#   entry       fma(pc, g1, qc g2) (colour), fma(twd, g3, fma(pd, g1, qd g2)) (depth): per term 19.5 + 19 u and the rounding of its
+#               product or fma (u), the depth row's outer fma u more                                                  <= 40.5 u
+# -> |a - exact| <= 41 u s, s = row_term_magnitudes (the magnitudes of the terms the entry combines, not |a|). The reference's
+# expression order (the oracle: IEEE, no rcp / rsq, the weight planes at 9 u) needs fewer.
+C_ROW_A = 41.0
+# B: bct = twc dct: 10.5 + 1 = 11.5 u;  bdt = twd ddt: 9.5 u, ddt = dn - dw u, the product u = 11.5 u. Relative: no cancellation.
+C_ROW_B = 12.0
+# prior term 1 - kz |dn - dw|: the difference u, the product u -> 2 u kz |ddt|; the outer difference u |t|
+#   integer sums (Q32.32): every term truncated to 2^-32, the int64 sum exact; (float)(sum 2^-32): u; / count: u
+#   float order: n float additions of the terms gamma_n sum |t|; / count: u
+#   fp64 sums rounded to float (the oracle's exact_sums hook): u; / count: u
+FIX_PRIOR_Q = 2.0 ** -32
+
+
+def _inner(shape):
+    m = np.zeros(shape, bool)
+    m[1:-1, 1:-1] = True
+    return m
+
+
+def coord_reference(d_new, i_new, d_warp, i_warp, behind_camera="product"):
+    """calculateCoord (:393-430) and the temporal derivatives (:477-478) from the NEW and WARPED planes of the level.
+
+    behind_camera: what becomes of a pixel whose warped depth is negative (a point warped behind the camera that still projects
+    into the image). "reference": nothing special (the reference, the oracle with its switch off, the reference-order build).
+    "product": it is not in validPixels, stays non-Null, and its stored warped depth is |dw| -- so `ddt` is dn - |dw| there
+    (the prior reads it; sf_solver.h, solve_linearise).
+    Every value is one float operation on float inputs: the bound is 1/2 ulp (`check_planes(..., c=0, half_ulp=True)`); Null and
+    validPixels are exact. Returns a dict of (rows, cols) arrays."""
+    assert behind_camera in ("product", "reference")
+    dn, i_n, dw, iw = (np.asarray(a, np.float32).astype(np.float64) for a in (d_new, i_new, d_warp, i_warp))
+    null = ~((dn != 0.0) & (dw != 0.0))
+    valid = ~null & _inner(dn.shape)
+    dwp = dw
+    if behind_camera == "product":
+        valid &= dw > 0.0
+        dwp = np.abs(dw)
+    return dict(null=null, valid=valid, depth=np.where(null, 0.0, 0.5 * (dn + dw)), intensity=0.5 * (i_n + iw), dct=i_n - iw,
+                ddt=dn - dwp, n_behind=int((~null & _inner(dn.shape) & (dw < 0.0)).sum()))
+
+
+def _edge_aware(X, null, eps):
+    """the four-neighbour stencil of :448-474 on one Inter plane -> (du, dv, m_u, m_v) on the inner pixels that are not Null, 0
+    elsewhere. r = 1 where the left / upper neighbour is Null (its rx / ry keep the fill value of :436-439)."""
+    du, dv, mu, mv = (np.zeros(X.shape) for _ in range(4))
+    c = X[1:-1, 1:-1]
+    ok = ~null[1:-1, 1:-1]
+    for out, mag, lo, hi, nlo in ((du, mu, X[1:-1, :-2], X[1:-1, 2:], null[1:-1, :-2]), (dv, mv, X[:-2, 1:-1], X[2:, 1:-1], null[:-2, 1:-1])):
+        d_hi, d_lo = hi - c, c - lo
+        r_c = np.abs(d_hi) + eps
+        r_lo = np.where(nlo, 1.0, np.abs(d_lo) + eps)
+        den = r_c + r_lo
+        out[1:-1, 1:-1] = np.where(ok, (r_lo * d_hi + r_c * d_lo) / den, 0.0)
+        mag[1:-1, 1:-1] = np.where(ok, (np.abs(r_lo * d_hi) + np.abs(r_c * d_lo)) / den, 0.0)
+    return du, dv, mu, mv
+
+
+def gradient_reference(depth_inter, intensity_inter, null):
+    """calculateDerivatives' spatial part (:432-474) from the implementation's own INTER depth and intensity planes and Null.
+    Returns dcu, dcv, ddu, ddv and their term magnitudes m_dcu ... (|r_l D_r| + |r_c D_l|) / (r_c + r_l): a float evaluation is
+    within C_GRADIENT u m + 1/2 ulp(value). Defined on the inner non-Null pixels; the caller masks with its validPixels (the
+    planes are exactly 0 outside them)."""
+    D = np.asarray(depth_inter, np.float32).astype(np.float64)
+    I = np.asarray(intensity_inter, np.float32).astype(np.float64)
+    null = np.asarray(null) != 0
+    dcu, dcv, mcu, mcv = _edge_aware(I, null, EPS_INTENSITY)
+    ddu, ddv, mdu, mdv = _edge_aware(D, null, EPS_DEPTH)
+    return dict(dcu=dcu, dcv=dcv, ddu=ddu, ddv=ddv, m_dcu=mcu, m_dcv=mcv, m_ddu=mdu, m_ddv=mdv)
+
+
+def check_planes(got, exact, valid, c=0.0, mag=None, relative=False, half_ulp=True):
+    """max over `valid` of |got - exact| / bound, bound = c u (mag, or |exact| when relative) + 1/2 ulp(exact) -- and whether the
+    plane is exactly 0 outside `valid`. -> (ratio, (v, u) of the worst pixel, zero_outside)"""
+    got = np.asarray(got, np.float64)
+    scale = np.abs(exact) if relative or mag is None else mag
+    bound = SECOND_ORDER * c * U32 * scale + (0.5 * ulp32(exact) if half_ulp else 0.0) + 1e-300
+    r = np.where(valid, np.abs(got - exact) / bound, 0.0)
+    r = np.where(np.isfinite(r), r, np.inf)
+    at = np.unravel_index(int(np.argmax(r)), r.shape)
+    return float(r.max()), tuple(int(k) for k in at), bool(np.all(got[~valid] == 0.0))
+
+
+def weights_reference(dcu, dcv, dct, ddu, ddv, ddt, valid):
+    """computeWeights (:481-510) from the implementation's six derivative planes on its validPixels: the raw pre-weights
+    1 / sqrt(e_m + k (|t| + |u| + |v|)), their maxima, and the normalised planes (0 outside validPixels).
+    IEEE evaluation (the oracle; the planes sf_get_lin_plane recomputes on the host with the device's 1 / max): raw within
+    C_WEIGHT_RAW u, normalised within C_WEIGHT u, relative. The weights the product's KERNELS use (rsq, rcp at 1 ulp) are seen
+    through the rows only (rows_reference)."""
+    p = [np.abs(np.asarray(a, np.float32).astype(np.float64)) for a in (dcu, dcv, dct, ddu, ddv, ddt)]
+    e_c = K_DUVT_C * (p[2] + p[0] + p[1])
+    e_d = K_DUVT_D * (p[5] + p[3] + p[4])
+    raw_c = np.where(valid, 1.0 / np.sqrt(ERR_M_C + e_c), 0.0)
+    raw_d = np.where(valid, 1.0 / np.sqrt(ERR_M_D + e_d), 0.0)
+    max_c, max_d = (float(r.max()) if valid.any() else 0.0 for r in (raw_c, raw_d))
+    return dict(raw_c=raw_c, raw_d=raw_d, max_c=max_c, max_d=max_d, wc=raw_c / max_c if max_c else raw_c, wd=raw_d / max_d if max_d else raw_d,
+                min_e_c=float(e_c[valid].min()) if valid.any() else np.inf, min_e_d=float(e_d[valid].min()) if valid.any() else np.inf)
+
+
+def focal_length(cols, tan_half_fovh):
+    """f = float(cols) / (2.f * tan) in float32 (:537)"""
+    return float(np.float32(cols) / (np.float32(2.0) * np.float32(tan_half_fovh)))
+
+
+def rows_reference(dcu, dcv, dct, ddu, ddv, d_new, d_warp, wc, wd, valid, tan_half_fovh, k_photometric_res):
+    """The Jacobian rows (:535-586) in fp64: A (2N x 6) and B (2N) in validPixels order (u outer, v inner; the colour row of a
+    pixel, then its depth row), from the implementation's derivative planes, the NEW and WARPED depth of the level and the EXACT
+    normalised weights of weights_reference -- so this is the check that sees the weights the kernels themselves evaluate
+    (fact_from_record: rsq of the stored planes times the device's 1 / max), which sf_get_lin_plane does not return.
+
+    ddt = dn - dw, d = (dn + dw) / 2, x = (u - disp_u) d / f, y = (v - disp_v) d / f. The Inter coordinates are 0.5 (xx + xxWarped)
+    with xxWarped = (u - disp_u) dw (1 / f) after a warp and the pyramid's (inv_f_i (u - disp_u)) dw on a first iteration
+    (Warped := Pred): the same number in exact arithmetic, two float associations -- both inside the count of C_ROW_A.
+    Returns A, B and x, y, d per valid pixel (for row_term_magnitudes)."""
+    rows, cols = np.shape(d_new)
+    f = focal_length(cols, tan_half_fovh)
+    sel = np.asarray(valid).T.ravel()
+    col = lambda a: np.asarray(a, np.float64).T.ravel()[sel]
+    uu, vv = np.meshgrid(np.arange(cols, dtype=np.float64), np.arange(rows, dtype=np.float64))
+    dn, dw = col(np.asarray(d_new, np.float32)), col(np.asarray(d_warp, np.float32))
+    d = 0.5 * (dn + dw)
+    x = (col(uu) - 0.5 * (cols - 1)) * d / f
+    y = (col(vv) - 0.5 * (rows - 1)) * d / f
+    inv_d = 1.0 / d
+    kph = float(np.float32(k_photometric_res))
+    N = int(sel.sum())
+    A = np.zeros((2 * N, 6))
+    B = np.zeros(2 * N)
+    for half, (gu, gv, gt, w, one) in enumerate(((col(dcu), col(dcv), col(dct), col(wc) * kph, 0.0), (col(ddu), col(ddv), dn - dw, col(wd), 1.0))):
+        dy, dz = gu * f * inv_d, gv * f * inv_d
+        A[half::2, 0] = w * -dy
+        A[half::2, 1] = w * -dz
+        A[half::2, 2] = w * (one + dy * x * inv_d + dz * y * inv_d)
+        A[half::2, 3] = w * (one * y + dy * inv_d * y * x + dz * (y * y * inv_d + d))
+        A[half::2, 4] = w * (-one * x - dy * (x * x * inv_d + d) - dz * inv_d * y * x)
+        A[half::2, 5] = w * (dy * y - dz * x)
+        B[half::2] = w * -gt
+    return A, B, (x, y, d)
+
+
+def check_rows(A_got, B_got, A, B, xyd):
+    """-> (max |A_got - A| / (C_ROW_A u s), max |B_got - B| / (C_ROW_B u |B|), (row, column) of the worst A entry)"""
+    s = row_term_magnitudes(A, *xyd)
+    rA = np.abs(np.asarray(A_got, np.float64) - A) / (SECOND_ORDER * C_ROW_A * U32 * s + 1e-300)
+    rB = np.abs(np.asarray(B_got, np.float64) - B) / (SECOND_ORDER * C_ROW_B * U32 * np.abs(B) + 0.5 * ulp32(B) + 1e-300)
+    at = np.unravel_index(int(np.argmax(rA)), rA.shape) if rA.size else (0, 0)
+    return float(rA.max()) if rA.size else 0.0, float(rB.max()) if rB.size else 0.0, (int(at[0]), int(at[1]))
+
+
+def seg_prior_reference(d_new, d_warp, labels, kz, behind_camera="product", n_labels=24):
+    """computeSegPrior (SegmentationBackground.cpp:53-103) from the NEW and WARPED depth and the labels of the level.
+
+    The counts are exact. lambda_t_w is evaluated in float32 (the `ratio < 0.1f` branch is a decision: it must be bit-equal).
+    b_prior: the exact mean of t = 1 - kz |dn - dw| (|dw| in place of dw under the product's rule) over the non-Null pixels of
+    the cluster, clamped to [-1, 2] (1-Lipschitz), -1 on the starved branch, 0 for an empty cluster -- with one bound per
+    summation path (see the counts above C_ROW_B):
+        "integer":  mean e_t + 2^-32 + 2 u |mean|      (Q32.32 sums: the product builds)
+        "float":    mean e_t + gamma_n sum |t| / n + u |mean|   (the reference's order: the oracle, the reference-order build)
+        "fp64":     mean e_t + 2 u |mean|              (the oracle's exact_sums hook)
+    e_t = u |t| + 2 u kz |ddt| is the float evaluation of one term. Returns a dict; `bound[path]` are arrays of n_labels."""
+    dn = np.asarray(d_new, np.float32).astype(np.float64)
+    dw = np.asarray(d_warp, np.float32).astype(np.float64)
+    if behind_camera == "product":
+        dw = np.abs(dw)
+    lab = np.asarray(labels).astype(np.int64)
+    kz = float(np.float32(kz))
+    member = lab != n_labels
+    nonnull = member & (dn != 0.0) & (dw != 0.0)
+    size = np.bincount(lab[member], minlength=n_labels)[:n_labels]
+    nn = np.bincount(lab[nonnull], minlength=n_labels)[:n_labels]
+    ddt = np.abs(dn - dw)[nonnull]
+    t = 1.0 - kz * ddt
+    e_t = U32 * np.abs(t) + 2 * U32 * kz * ddt
+    S = np.bincount(lab[nonnull], weights=t, minlength=n_labels)[:n_labels]
+    Sa = np.bincount(lab[nonnull], weights=np.abs(t), minlength=n_labels)[:n_labels]
+    Se = np.bincount(lab[nonnull], weights=e_t, minlength=n_labels)[:n_labels]
+    ratio = (nn.astype(np.float32) / np.maximum(size, 1).astype(np.float32)).astype(np.float32)  # float(nonnull) / float(size), :89
+    starved = (size > 0) & (ratio < np.float32(0.1))
+    lam = np.where(size > 0, np.where(starved, np.float32(0.1), ratio), np.float32(0)).astype(np.float32)
+    n = np.maximum(nn, 1).astype(np.float64)
+    mean = S / n
+    full = (size > 0) & ~starved
+    b = np.where(full, np.clip(mean, -1.0, 2.0), np.where(starved, -1.0, 0.0))
+    me, am = Se / n * SECOND_ORDER, np.abs(mean)
+    z = np.zeros(n_labels)
+    bound = {"integer": np.where(full, me + FIX_PRIOR_Q + 2 * U32 * am, z),
+             "float": np.where(full, me + gamma(nn) * Sa / n + U32 * am, z),
+             "fp64": np.where(full, me + 2 * U32 * am, z)}
+    return dict(size=size, nonnull=nn, lambda_t_w=lam, b_prior=b, bound=bound, starved=starved, full=full, terms=t, term_labels=lab[nonnull],
+                sum=S)
