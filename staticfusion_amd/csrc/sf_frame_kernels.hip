@@ -1,7 +1,9 @@
 // sf_frame_kernels.hip — the persistent frame kernel (and the isolated IRLS pass kernel) of libsf_hip.so.
-// Compiled twice into the library: -DSF_NT=256 (throughput variant) and -DSF_NT=1024 (latency variant); every
-// workgroup-size dependent constant (waves per workgroup, tile and window sizes, LDS layout) derives from SF_NT.
-// The host side (sf_hip.hip) reaches the kernels through the two extern "C" launchers at the end.
+// Compiled several times into the library (the object table of the Makefile; the axes and their defaults: sf_build_config.h),
+// among them -DSF_NT=256 (throughput variant) and -DSF_NT=1024 (latency variant); every workgroup-size dependent constant
+// (waves per workgroup, tile and window sizes, LDS layout) derives from SF_NT. One header per stage: sf_pyramid.h, sf_kmeans.h
+// (sf_kmeans_cluster.h), sf_solver.h (the map of the solver's stage headers), sf_residuals.h.
+// The host side (sf_hip.hip) reaches the kernels through the extern "C" launchers at the end.
 #include <hip/hip_runtime.h>
 
 #include "sf_cluster.h"
@@ -14,11 +16,8 @@
 #include "sf_residuals.h"
 #include "sf_smallmath.h"
 #include "sf_solver.h"
+#include "sf_solver_support.h"
 
-#ifndef SF_OCC
-#define SF_OCC 4
-#endif
-#define SF_BLOCKS_PER_CU (SF_OCC * 256 / SF_NT)  // 16 waves per CU at <= 128 VGPRs (5 x 256 per CU measured 3 % slower: DESIGN.md §9)
 // __launch_bounds__(threads, 4): the second HIP parameter is the minimum number of WAVES PER SIMD, not workgroups per
 // CU: 4 waves per SIMD = 16 waves per CU = <= 128 VGPRs for every workgroup size
 #define SF_PASTE2(a, b) a##b

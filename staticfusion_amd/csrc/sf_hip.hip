@@ -8,26 +8,25 @@
 //
 // There is no CPU fallback and no dependence on the test oracle.
 #include "sf_host.h"
+#include "sf_reforder.h"  // RO_LIST_K: the size of the source lists
 
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_frame_nt256(int, hipStream_t, const KArgs *, const FrameLaunch *);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_irls_pass_nt256(int, hipStream_t, const KArgs *, int, int, int, int);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_frame_nt256o5(int, hipStream_t, const KArgs *, const FrameLaunch *);
-extern "C" __attribute__((visibility("hidden"))) void sf_variant_geometry_nt256o5(int *, int *);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_frame_nt1024(int, hipStream_t, const KArgs *, const FrameLaunch *);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_irls_pass_nt1024(int, hipStream_t, const KArgs *, int, int, int, int);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_debug_rows_nt256(int, hipStream_t, const KArgs *, int, float *);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_debug_rows_nt1024(int, hipStream_t, const KArgs *, int, float *);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_frame_ntcluster(int, hipStream_t, const KArgs *, const FrameLaunch *);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_irls_pass_ntcluster(int, hipStream_t, const KArgs *, int, int, int, int);
-extern "C" __attribute__((visibility("hidden"))) void sf_launch_debug_rows_ntcluster(int, hipStream_t, const KArgs *, int, float *);
-extern "C" __attribute__((visibility("hidden"))) void sf_variant_geometry_ntcluster(int *, int *);
-extern "C" __attribute__((visibility("hidden"))) void sf_variant_geometry_nt256(int *, int *);
-extern "C" __attribute__((visibility("hidden"))) void sf_variant_geometry_nt1024(int *, int *);
-extern "C" __attribute__((visibility("hidden"))) int sf_variant_flags_nt256(void);
+// what every frame object defines under its variant tag (sf_frame_kernels.hip: SF_VARIANT_FN; the tags: csrc/Makefile)
+#define SF_DECLARE_VARIANT(tag)                                                                                  \
+    extern "C" SF_INTERNAL void sf_launch_frame_nt##tag(int, hipStream_t, const KArgs *, const FrameLaunch *);    \
+    extern "C" SF_INTERNAL void sf_launch_irls_pass_nt##tag(int, hipStream_t, const KArgs *, int, int, int, int); \
+    extern "C" SF_INTERNAL void sf_launch_debug_rows_nt##tag(int, hipStream_t, const KArgs *, int, float *);      \
+    extern "C" SF_INTERNAL void sf_variant_geometry_nt##tag(int *, int *);                                        \
+    extern "C" SF_INTERNAL int sf_variant_flags_nt##tag(void);
+SF_DECLARE_VARIANT(256)
+SF_DECLARE_VARIANT(256o5)
+SF_DECLARE_VARIANT(1024)
+SF_DECLARE_VARIANT(cluster)
+#define SF_VARIANT_ROW(id, name, tag) \
+    {id, name, sf_variant_geometry_nt##tag, sf_launch_frame_nt##tag, sf_launch_irls_pass_nt##tag, sf_launch_debug_rows_nt##tag}
 static const FrameVariant VARIANTS[3] = {
-    {SF_VARIANT_THROUGHPUT, "throughput", sf_variant_geometry_nt256, sf_launch_frame_nt256, sf_launch_irls_pass_nt256, sf_launch_debug_rows_nt256},
-    {SF_VARIANT_LATENCY, "latency", sf_variant_geometry_nt1024, sf_launch_frame_nt1024, sf_launch_irls_pass_nt1024, sf_launch_debug_rows_nt1024},
-    {SF_VARIANT_CLUSTER, "cluster", sf_variant_geometry_ntcluster, sf_launch_frame_ntcluster, sf_launch_irls_pass_ntcluster, sf_launch_debug_rows_ntcluster},
+    SF_VARIANT_ROW(SF_VARIANT_THROUGHPUT, "throughput", 256),
+    SF_VARIANT_ROW(SF_VARIANT_LATENCY, "latency", 1024),
+    SF_VARIANT_ROW(SF_VARIANT_CLUSTER, "cluster", cluster),
 };
 
 // Longest-expected-first order of the streams of a launch (KArgs::order): a counting sort by the IRLS iterations each

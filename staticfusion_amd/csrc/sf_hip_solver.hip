@@ -449,7 +449,7 @@ int sf_get_lin_plane(sf_handle *h, int stream, int which, float *out, int *rows,
     if (int e = d2h(h, dn.data(), h->k.pyr_new[0] + (size_t)stream * h->k.n_tot + h->k.loff[L], sizeof(float) * n)) return e;
     if (int e = d2h(h, dw.data(), h->k.rec[R_DW] + o, sizeof(float) * n)) return e;
     auto fetch = [&](int plane, std::vector<float> &v) { v.resize(n); return d2h(h, v.data(), h->k.rec[plane] + o, sizeof(float) * n); };
-    std::vector<uint8_t> lab(n);  // validPixels: the sign of the stored warped depth (sf_solver.h, linearise)
+    std::vector<uint8_t> lab(n);  // validPixels: the sign of the stored warped depth (sf_linearise.h)
     if (h->reforder) {  // ... or, in the reference-order build, the label plane (the sign there is the warp's own)
         if (int e = d2h(h, lab.data(), h->k.rec_lab + o, n)) return e;
     } else

@@ -27,6 +27,9 @@
 // Performance is irrelevant here (a QVGA frame takes tens of milliseconds on one workgroup); one workgroup per stream only.
 #pragma once
 
+#include "sf_device_common.h"
+#include "sf_splat.h"  // SplatGeom, SplatWin
+
 #define RO_LIST_K 32     // source pixels remembered per target cell; a cell with more is summed by a scan over the level
 
 // ---------------------------------------------------------------------------------------------
@@ -36,12 +39,10 @@
 //  iteration-count mismatches away (5000 sequences at 160 x 120: 38 -> 22 frames, 25 -> 14). Levels of at most
 //  SF_ORDERED_SPLAT_MAX_PIXELS pixels (QVGA: image levels 3 and 4, 1.5 % of the pyramid's pixels; with 8192 -- level 2 as well --
 //  the excursions were the same within their noise and the cost double) take the ordered splat below in every build of the
-//  product; larger levels keep the exact integer sums (sf_device_common.h). The per-cell source lists of the fall-back are
+//  product; larger levels keep the exact integer sums (sf_splat.h). The per-cell source lists of the fall-back are
 //  scratch of the WORKGROUP that runs the warp (KArgs::ro_list: one block of 256 KB per stream or resident workgroup).
+//  (SF_ORDERED_SPLAT_MAX_PIXELS: sf_build_config.h)
 // ---------------------------------------------------------------------------------------------
-#ifndef SF_ORDERED_SPLAT_MAX_PIXELS
-#define SF_ORDERED_SPLAT_MAX_PIXELS 2048  // (<= SF_CLUSTER_SOLO_PIXELS: a cluster's workgroups run such levels each on its own)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 //  the splat of warpImagesAccurateInverse / computeResidualsAgainstPreviousImage in the reference's order

@@ -1,5 +1,5 @@
 // sf_reforder_solver.h — the solver stages of the REFERENCE-ORDER build (sf_reforder.h has the what and why).
-// Included by sf_solver.h behind SolveShared / IrlsCtx; replaces solve_seg_prior, the initial mean |res| and the two IRLS
+// Included by sf_irls.h behind SolveShared / IrlsCtx; replaces solve_seg_prior, the initial mean |res| and the two IRLS
 // passes. One pixel per lane and trip, plain indexed loads: nothing here is tuned.
 #pragma once
 

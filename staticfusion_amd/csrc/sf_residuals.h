@@ -6,7 +6,9 @@
 
 #include "sf_cluster.h"
 #include "sf_device_common.h"
+#include "sf_reforder.h"  // splat_ordered, ordered_splat, ro_list_of, ro_unpack_cell
 #include "sf_smallmath.h"
+#include "sf_splat.h"
 
 struct ResShared {
     float Tinv[16];

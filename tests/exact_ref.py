@@ -162,7 +162,7 @@ def warp_reference(depth, intensity, xx, yy, T_odometry, tan_half_fovh):
 def warp_bounds(ref, ordered):
     """Per-cell tolerances (depth, intensity) of a checked, touched cell.
 
-    integer path (exact fixed-point sums, sf_device_common.h): each contribution enters as trunc(w depth_w^ 2^26) -- the weighted
+    integer path (exact fixed-point sums, sf_splat.h): each contribution enters as trunc(w depth_w^ 2^26) -- the weighted
     mean of those truncations is within 2^-26 of the mean of w depth_w^ (2^-28 for intensity); depth_w^ is within e_d of the
     exact depth_w; the int64 -> float conversion and the division round twice: 2 ulp of the result.
         |gpu - ref| <= 2 ulp(ref) + q + sum w e_d / sum w
@@ -223,7 +223,7 @@ def irls_weights(B, b_row, kc_cauchy):
 
 def row_term_magnitudes(A, x, y, d):
     """Per row and entry, the sum of the magnitudes of the terms the product's factored rows combine into that entry
-    (sf_solver.h, PixFact: a_c = P g1 + Q g2, a_d = W g3 + P g1 + Q g2 with P = -a_0, Q = -a_1, g1 = [-1, 0, x/d, xy/d,
+    (sf_irls.h, PixFact: a_c = P g1 + Q g2, a_d = W g3 + P g1 + Q g2 with P = -a_0, Q = -a_1, g1 = [-1, 0, x/d, xy/d,
     -(x^2/d + d), y], g2 = [0, -1, y/d, y^2/d + d, -xy/d, -x], g3 = [0, 0, 1, y, -x, 0]): a computed entry is off by a few u of
     THIS, not of |a|, where its terms cancel. x, y, d: the Inter planes at each row's pixel (2 rows per pixel)."""
     A = np.asarray(A, np.float64)
@@ -389,7 +389,7 @@ C_GRADIENT = 8.0
 C_WEIGHT_RAW = 3.5
 # normalised: the maximum is one of the raw values (3.5 u), 1.f / max: + u = 4.5 u, times the raw value (3.5 u), rounded (u): 9 u
 C_WEIGHT = 9.0
-# The product's kernels (fact_from_record + debug_rows of sf_solver.h), from the stored derivative planes:
+# The product's kernels (fact_from_record of sf_irls.h + debug_rows of sf_solver_support.h), from the stored derivative planes:
 #   pre-weight  twc = (inv_max_c rsq(1 + e)) kph:  argument 4 u -> 2 u, rsq 1 ulp = 2 u, inv_max_c 4.5 u (above: its minimum-e
 #               argument 4 u, 1 / x u, sqrt -> 3.5 u, 1 / max u), two products 2 u                                       = 10.5 u
 #               (twd = inv_max_d rsq(0.01 + e): one product less, 9.5 u)
@@ -425,7 +425,7 @@ def coord_reference(d_new, i_new, d_warp, i_warp, behind_camera="product"):
     behind_camera: what becomes of a pixel whose warped depth is negative (a point warped behind the camera that still projects
     into the image). "reference": nothing special (the reference, the oracle with its switch off, the reference-order build).
     "product": it is not in validPixels, stays non-Null, and its stored warped depth is |dw| -- so `ddt` is dn - |dw| there
-    (the prior reads it; sf_solver.h, solve_linearise).
+    (the prior reads it; sf_linearise.h, solve_linearise).
     Every value is one float operation on float inputs: the bound is 1/2 ulp (`check_planes(..., c=0, half_ulp=True)`); Null and
     validPixels are exact. Returns a dict of (rows, cols) arrays."""
     assert behind_camera in ("product", "reference")

@@ -31,7 +31,7 @@ from staticfusion_amd.synth import make_pair
 from test_exact_references import SCENES, irls_solver, solve, tan_half_fovh
 
 PRODUCT = ("throughput", "latency", "cluster")
-LS_ROWS = 62  # rows of a register strip (sf_solver.h)
+LS_ROWS = 62  # rows of a register strip (sf_solve_shared.h)
 LIN = dict(dcu=capi.LIN_DCU, dcv=capi.LIN_DCV, dct=capi.LIN_DCT, ddu=capi.LIN_DDU, ddv=capi.LIN_DDV, ddt=capi.LIN_DDT, wc=capi.LIN_WC,
            wd=capi.LIN_WD)
 STAGES = ("coord", "gradients", "weights", "rows_A", "rows_B", "prior")

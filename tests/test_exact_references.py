@@ -125,7 +125,7 @@ def ordered_levels(kind, s):
 
 def warp_checks(s, kind, name, stream=0):
     """(level, exact reference, failures, stats) of every checked level: the reference warps the PRED planes with the T_odometry
-    that solve_warp read -- the trace's T of the outer iteration before the level's last one (sf_solver.h: solve_warp)."""
+    that solve_warp read -- the trace's T of the outer iteration before the level's last one (sf_warp.h: solve_warp)."""
     _, _, _, _, levels, _ = SCENES[name]
     st = s.stats(stream)
     lv = np.array([st.outer[i].level for i in range(st.n_outer)])

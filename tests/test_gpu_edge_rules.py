@@ -6,7 +6,7 @@
 2. A point warped BEHIND the camera that still projects into the image (a diverged pose, or -- here -- a surface closer to
    the camera than the frame-to-frame motion): the reference keeps such a pixel in validPixels (FrontEnd.cpp:816-823 has no
    depth test). The HIP build leaves it out -- the sign of the stored warped depth is what marks validPixels for the
-   streaming passes (sf_solver.h, solve_linearise) -- and gives computeSegPrior its magnitude. The oracle carries the same
+   streaming passes (sf_linearise.h, solve_linearise) -- and gives computeSegPrior its magnitude. The oracle carries the same
    rule behind a switch (sfo_test_set_hip_behind_camera_rule): with it, HIP and oracle agree as on any other input; without
    it the valid-pixel counts differ by exactly the pixels the oracle reports as behind the camera.
 """
@@ -123,7 +123,7 @@ def test_points_warped_behind_the_camera(hip, ora):
 
 def test_first_touch_splat_on_odd_geometry(hip, ora):
     """The one-workgroup builds' splat keeps no zeroed accumulator image: a window's flush STORES the cells nobody has written
-    yet (a row watermark per column says which, sf_device_common.h) in groups of 16 rows. What that bookkeeping has to get
+    yet (a row watermark per column says which, sf_splat.h) in groups of 16 rows. What that bookkeeping has to get
     right, all in one scene: rows that are not a multiple of 16 (200: the last group of a column is short), source tiles
     without a valid pixel (three strips of 16 predicted columns are holes: their windows do not exist, the columns they would
     have reached are zeroed at the end), a block of holes at the top of another strip (its first window starts far down: the

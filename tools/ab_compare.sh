@@ -4,10 +4,10 @@
 #   tools/build_variant.sh <tag> "<-D flags>"          builds staticfusion_amd/csrc/libsf_hip_<tag>.so here (it travels with gpurun)
 #   gpurun --timeout 1200 -- 'bash tools/ab_compare.sh libsf_hip.so libsf_hip_<tag>.so [reps=3] [batch=5120] [stage ...]'
 # prints frames/s of both workloads of the bench line per repetition and the mean ratio B / A; extra arguments are names of
-# in-kernel stage timers (tools/stage_profile.py) to print beside them, e.g. warp residuals.
-set -u
+# in-kernel stage timers (tools/stage_profile.py) to print beside them, e.g. warp residuals. Ends at the first run that fails.
+set -eu -o pipefail
 cd "$(dirname "$0")/.."
-A=$1; B=$2; REPS=${3:-3}; BATCH=${4:-5120}; shift; shift; shift 2>/dev/null; shift 2>/dev/null
+A=$1; B=$2; REPS=${3:-3}; BATCH=${4:-5120}; shift; shift; shift 2>/dev/null || true; shift 2>/dev/null || true
 STAGES="$*"
 C=$PWD/staticfusion_amd/csrc
 TMP=$(mktemp)
@@ -18,7 +18,7 @@ for r in $(seq 1 $REPS); do
       out=$(SF_HIP_LIB=$C/$lib timeout -k 10 300 python tools/stage_profile.py --batch $BATCH --workload $w --steps 10)
       fps=$(echo "$out" | grep workload | sed -E 's/.* ([0-9]+) frames\/s.*/\1/')
       extra=""
-      for s in $STAGES; do extra="$extra $s=$(echo "$out" | grep -E "^ +$s " | awk '{print $2}')us"; done
+      for s in $STAGES; do extra="$extra $s=$(echo "$out" | { grep -E "^ +$s " || true; } | awk '{print $2}')us"; done
       echo "rep $r $w $lib: $fps frames/s$extra"
       echo "$w $lib $fps" >> $TMP
     done

@@ -6,7 +6,8 @@
 # frames per launch (sequences only): K > 0 measures ONE launch of K frames of every stream -- what bench.py times (the launch
 # skips createImagePyramid(true) for the frames whose pyramid buffers swap and advances the streams itself) -- instead of one
 # launch per frame; hbm_bytes_per_launch is then divided by K, and bench.py only accepts the file for the same K.
-set -u
+# Ends at the first step that fails.
+set -eu -o pipefail
 WL=$1; B=$2; VAR=${3:-throughput}; K=${4:-0}
 cd "$(dirname "$0")/.."
 TAG=traffic_${WL}_b${B}

@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <cmath>
 #include <vector>
-#include "sf_device_common.h"
+#include "sf_reforder.h"
 
 struct Src {
     gptr<const float> d, i;

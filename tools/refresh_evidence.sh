@@ -1,8 +1,10 @@
 #!/bin/bash
 # after a change of the device sources: PMC traffic of the four workloads of the bench line (tagged with the new source hash),
 # the bench line with it, the GPU test suite, the distance of both library builds from the oracle
-set -u
-cd "$GRAFT_REPO_ROOT" 2>/dev/null || true
+# Every step has its own time limit and the script ends at the first step that fails: nothing more is started on a GPU
+# that has just faulted or hung.
+set -eu -o pipefail
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out profiles; export TMPDIR=/tmp
 T=${1:-r03i}
 for spec in "static 16384" "sphere 16384" "sequences 4096" "sequences 16384"; do

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence for one workload: kernel-trace stats + HBM byte counters
-# (separate --pmc passes, as MI355X_MICROARCH.md prescribes). Run ON THE GPU BOX via gpurun.
+# (separate --pmc passes, as MI355X_MICROARCH.md prescribes). Run on the GPU box.
 # usage: tools/rocprof_collect.sh <tag> <workload> <batch>
-set -u
+# Ends at the first step that fails or runs into its time limit: nothing more is started on a GPU that has just faulted.
+set -eu -o pipefail
 TAG=$1; WL=$2; B=$3
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
@@ -21,4 +22,4 @@ if [ "${SF_PROF_SQ:-0}" = "1" ]; then
   timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_SALU -d $OUT/sq -o sq -- $CMD > $OUT/sq.log 2>&1
   timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE -d $OUT/grbm -o grbm -- $CMD > $OUT/grbm.log 2>&1
 fi
-find $OUT -name "*.csv" | head -20
+find $OUT -name "*.csv" | sed -n 1,20p
