@@ -467,8 +467,10 @@ int SF_FN(get_stage_profile)(sf_handle *h, int64_t ticks[32]);
  * solve, one launch of sf_irls_pass_kernel. variant 0 = product code; 1 = loads only; 2 = no
  * accumulation (ablations); variant | (S << 8) splits every level into S pixel ranges walked by S different
  * workgroups (how fast the passes run when fewer streams are in flight and their records stay in the
- * Infinity Cache; an experiment, partial sums are not combined). Elapsed HIP-event milliseconds of the
- * launch. Not part of a solve. */
+ * Infinity Cache; an experiment, partial sums are not combined). which 3 / 4: pass 1 then pass 2 back to back over the
+ * same records, `reps` times -- pass 2 upwards like pass 1 (3) or back down from where pass 1 ended (4, the order of the
+ * solver); which | (L << 4) walks level L's pixel count with its geometry (timing only: the record values are level 0's).
+ * Elapsed HIP-event milliseconds of the launch. Not part of a solve. */
 int SF_FN(microbench_pass)(sf_handle *h, int which, int variant, int reps, float *elapsed_ms);
 /* Forget a timeout (SF_STATUS_SYNC_TIMEOUT) of every stream of the handle after the handle's stream has drained.
  * SF_VARIANT_CLUSTER: granules, epochs and the sticky flag of the rendezvous are reset; the solver state is left as it is.

@@ -50,7 +50,8 @@ enum {
     ST_RESIDUALS = 16,   // computeResidualsAgainstPreviousImage(index)
     ST_SEGM_IMAGE = 32,  // buildSegmImage
     ST_PUSH_HISTORY = 64, // ring[im_count % 5] = current
-    ST_AUTO_RESIDUALS = 128 // several frames per launch: ST_RESIDUALS from the frame with im_count >= SF_HISTORY on
+    ST_AUTO_RESIDUALS = 128, // several frames per launch: ST_RESIDUALS from the frame with im_count >= SF_HISTORY on
+    ST_SOLVER_FORWARD = 256  // test and A/B support: IRLS pass 2 walks its records upwards like pass 1 (sf_irls.h), not back down
 };
 
 // Several consecutive frames of every stream in ONE launch of the frame kernel (sf_process_frames /

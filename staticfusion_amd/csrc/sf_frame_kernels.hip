@@ -73,7 +73,7 @@ __device__ __forceinline__ void run_stages(const KArgs &a, int b, int stage_mask
         cluster_barrier(cs, tid);  // the labels of every level are visible to every workgroup of the cluster
     }
     if (stage_mask & ST_SOLVE) {
-        stage_solve(a, b, *(LDS SolveShared *)&sh.sv, cs, tid);
+        stage_solve(a, b, (stage_mask & ST_SOLVER_FORWARD) != 0, *(LDS SolveShared *)&sh.sv, cs, tid);
         t0 = wall_clock64();
     }
     // the frame loop pushes the current images into the ring slot the residual stage has just read (im_count % 5 both):
@@ -360,15 +360,15 @@ __global__ __launch_bounds__(SF_NT, 4) void sf_irls_pass_kernel(const KArgs *__r
             }
             break;
         }
-        if (which == 1) {
-            if (variant == 0) microbench_pass<1, 0>(a, b, slice, slices, reps, *(LDS SolveShared *)&sh.sv, tid);
-            if (variant == 1) microbench_pass<1, 1>(a, b, slice, slices, reps, *(LDS SolveShared *)&sh.sv, tid);
-            if (variant == 2) microbench_pass<1, 2>(a, b, slice, slices, reps, *(LDS SolveShared *)&sh.sv, tid);
-        } else {
-            if (variant == 0) microbench_pass<2, 0>(a, b, slice, slices, reps, *(LDS SolveShared *)&sh.sv, tid);
-            if (variant == 1) microbench_pass<2, 1>(a, b, slice, slices, reps, *(LDS SolveShared *)&sh.sv, tid);
-            if (variant == 2) microbench_pass<2, 2>(a, b, slice, slices, reps, *(LDS SolveShared *)&sh.sv, tid);
-        }
+        LDS SolveShared &sv = *(LDS SolveShared *)&sh.sv;
+        const int L = which >> 4;  // bits 4.. of `which`: the level whose size and geometry the passes walk (sf_solver_support.h)
+#define SF_MB_CASE(W, V) \
+    if ((which & 15) == W && variant == V) microbench_pass<W, V>(a, b, L, slice, slices, reps, sv, tid)
+        SF_MB_CASE(1, 0); SF_MB_CASE(1, 1); SF_MB_CASE(1, 2);
+        SF_MB_CASE(2, 0); SF_MB_CASE(2, 1); SF_MB_CASE(2, 2);
+        SF_MB_CASE(3, 0); SF_MB_CASE(3, 1); SF_MB_CASE(3, 2);  // pass 1 then pass 2, both upwards
+        SF_MB_CASE(4, 0); SF_MB_CASE(4, 1); SF_MB_CASE(4, 2);  // pass 1 upwards, pass 2 back down
+#undef SF_MB_CASE
         __syncthreads();
     }
 }

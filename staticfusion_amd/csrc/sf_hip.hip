@@ -127,6 +127,9 @@ int launch(sf_handle *h, int mask, int im_count, int n_frames, const FrameLaunch
     // test support (tests/test_multi_frame.py): frame k of every third stream is given up once its previous frame is done -- the
     // path of a wait that ran into its bound, which nothing else can provoke
     if (const char *v = std::getenv("SF_DEBUG_GIVE_UP_AT_FRAME")) fl.debug_give_up = (int)std::strtol(v, nullptr, 10);
+    // test and A/B support (tests/test_gpu_serpentine.py, tools/ab_compare.sh): SF_SOLVER_FORWARD=1 walks the records of IRLS pass 2
+    // in the order of pass 1 instead of back down -- the same results up to the order of one fp64 sum (sf_irls.h)
+    if (const char *v = std::getenv("SF_SOLVER_FORWARD")) if (v[0] == '1') fl.stage_mask |= ST_SOLVER_FORWARD;
     const bool timed = (mask & ST_SOLVE) != 0;
     if (h->k.order && (mask & ST_SOLVE) && !std::getenv("SF_NO_STREAM_ORDER")) {
         // more streams than resident workgroups: hand the streams out longest-expected-first (their previous frame's IRLS

@@ -540,7 +540,8 @@ int sf_get_stage_profile(sf_handle *h, int64_t ticks[32]) {
 int sf_microbench_pass(sf_handle *h, int which, int variant, int reps, float *elapsed_ms) {
     const int slices = (variant >> 8) ? (variant >> 8) : 1;  // bits 8.. of `variant`: workgroups per stream (experiment)
     variant &= 255;
-    if (!h || (which != 1 && which != 2) || variant < 0 || variant > 2 || reps < 1 || slices > 64) return fail(SF_ERR_ARG, "bad argument");
+    // `which`: 1 / 2 one pass; 3 / 4 pass 1 then pass 2 (upwards / back down); | (L << 4) at level L's size and geometry
+    if (!h || (which & 15) < 1 || (which & 15) > 4 || (which >> 4) < 0 || (which >> 4) >= h->k.levels || variant < 0 || variant > 2 || reps < 1 || slices > 64) return fail(SF_ERR_ARG, "bad argument");
     if (h->fv->id == SF_VARIANT_CLUSTER) return fail(SF_ERR_STATE, "the isolated passes are not built for the cluster variant");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemsetAsync(h->k.queue, 0, sizeof(int), h->stream));

@@ -406,7 +406,11 @@ __device__ __forceinline__ unsigned long long to_fix32_pos(float x) {
 // Per-label sums: each lane keeps a running fixed-point sum for the label of its last pixel and
 // flushes it to the workgroup bins (LDS integer atomics: order-independent) only when the label
 // changes -- labels are spatially coherent, so flushes are rare.
-template <int VAR>
+// DIR: 0 walks the pairs of [begin, n) upwards, as pass 1 does; 1 walks the SAME pairs from the top down (the first trip covers
+// the last SF_NT pairs, i0 falls by SF_NT * 2 per trip, lanes keep ascending addresses inside a trip), so that the pass starts
+// on the records pass 1 has just read and ends at `begin`, where the next pass 1 starts. The per-label
+// sums are integers: the same bits in either direction; sq changes the order of its fp64 sum only.
+template <int VAR, int DIR = 0>
 __device__ __noinline__ void irls_pass2(const KArgs &a, int b, int L, LDS SolveShared &s, int tid) {
     const IrlsCtx c = make_irls_ctx(a, b, L, s);
     const int lane = tid & 63, wave = tid >> 6;
@@ -417,10 +421,14 @@ __device__ __noinline__ void irls_pass2(const KArgs &a, int b, int L, LDS SolveS
     int cur_lab = 0;
     unsigned long long cur_sum = 0;
     const int last = (c.n - 2) & ~1;
+    // DIR 1: the pair of lane 0 in the first trip lies SF_NT pairs below the end of the range (below `begin` in a range of fewer
+    // pairs: those lanes make no trip); begin is even, so every pair starts where a pair of the upward walk starts
+    const int step = DIR ? -SF_NT * 2 : SF_NT * 2;
+    const int start = (DIR ? c.begin + ((c.n - c.begin + 1) & ~1) - SF_NT * 2 : c.begin) + tid * 2;
     RecVec<2> rv, nx;
-    if (c.begin + tid * 2 < c.n) load_rec<2>(c.rp, c.begin + tid * 2, rv);
-    for (int i0 = c.begin + tid * 2; i0 < c.n; i0 += SF_NT * 2) {
-        load_rec<2>(c.rp, min(i0 + SF_NT * 2, last), nx);  // next pair in flight during this one
+    if (DIR ? start >= c.begin : start < c.n) load_rec<2>(c.rp, start, rv);
+    for (int i0 = start; DIR ? i0 >= c.begin : i0 < c.n; i0 += step) {
+        load_rec<2>(c.rp, DIR ? max(i0 + step, c.begin) : min(i0 + step, last), nx);  // next pair in flight during this one
         const bool ok0 = sanitize<2>(rv, 0), ok1 = sanitize<2>(rv, 1);
         if constexpr (VAR == 1) {
             float t = rv.dn[0] + rv.dn[1];
@@ -548,7 +556,7 @@ __device__ __noinline__ void irls_iteration_tail(const KArgs &a, LDS SolveShared
     }
 }
 
-__device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level, int kouter, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
+__device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level, int kouter, bool forward, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     const bool seg = a.p.segmentation_enabled != 0;
     const int N = __builtin_amdgcn_readfirstlane(s.n_valid);
@@ -627,7 +635,12 @@ __device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level,
 #if SF_REFORDER
         ro_pass2(a, b, L, s, tid);
 #else
-        irls_pass2<0>(a, b, L, s, tid);
+        // serpentine: pass 1 ends at the top of the records, pass 2 starts there and ends where the next pass 1 starts, so each
+        // pass begins on the lines its predecessor touched last (uniform branch; `forward` is the old order, for tests and A/B)
+        if (forward)
+            irls_pass2<0, 0>(a, b, L, s, tid);
+        else
+            irls_pass2<0, 1>(a, b, L, s, tid);
 #endif
         __syncthreads();
         irls_reduce_residuals(s, cs, tid);

@@ -46,7 +46,8 @@
 // them on its own (redundantly, on a private record slot) and all arrive at bit-identical state.
 #define SF_CLUSTER_SOLO_PIXELS 8192
 
-__device__ __noinline__ void stage_solve(const KArgs &a, int b, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
+// forward (uniform, from the launch: ST_SOLVER_FORWARD): pass 2 of the IRLS walks upwards like pass 1 -- tests and A/B only
+__device__ __noinline__ void stage_solve(const KArgs &a, int b, bool forward, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
     StreamState &st = a.state[b];
     if (tid < 16) s.T[tid] = (tid % 5 == 0) ? 1.f : 0.f;  // T_odometry.setIdentity()  (:1091)
     if (tid < 6) {
@@ -108,7 +109,7 @@ __device__ __noinline__ void stage_solve(const KArgs &a, int b, LDS SolveShared 
 #endif
 #endif
             PROF_MARK(s, tid, PF_LINEARISE);
-            solve_irls(a, b, L, i, k, s, cs, tid);
+            solve_irls(a, b, L, i, k, forward, s, cs, tid);
             if (tid == 0) {
                 s.n_outer++;
                 double s2 = 0.0;

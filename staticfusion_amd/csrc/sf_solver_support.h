@@ -59,9 +59,13 @@ __device__ __forceinline__ void debug_rows(const KArgs &a, int b, float *out, in
 // ---------------------------------------------------------------------------------------------
 //  measurement support: the two IRLS streaming passes in isolation, over the level-0 records the
 //  last solve left behind (tools/pass_microbench.py, sf_microbench_pass)
+//  WHICH 1 / 2: that pass alone. WHICH 3 / 4: one IRLS iteration's traffic, pass 1 then pass 2 back to back over the same
+//  range, pass 2 upwards (3) or back down (4: the serpentine order of solve_irls). L > 0 walks the first ln[L] pixels of the
+//  same record planes with that level's geometry and depth plane: the values mean nothing there, the bytes and the
+//  instructions are the level's (sanitize() keeps every row finite).
 // ---------------------------------------------------------------------------------------------
 template <int WHICH, int VAR>
-__device__ void microbench_pass(const KArgs &a, int b, int slice, int slices, int reps, LDS SolveShared &s, int tid) {
+__device__ void microbench_pass(const KArgs &a, int b, int L, int slice, int slices, int reps, LDS SolveShared &s, int tid) {
     const StreamState &st = a.state[b];
     if (tid < SF_NC) s.b_segm[tid] = a.p.segmentation_enabled ? st.b_segm[tid] : 1.f;
     if (tid < 6) s.Var[tid] = st.twist_level[tid];
@@ -71,19 +75,22 @@ __device__ void microbench_pass(const KArgs &a, int b, int slice, int slices, in
         s.rec_slot = b;
         s.aver_res = 0.002f;
         s.first = 0;
-        s.n_valid = a.ln[0];
-        const int per = ((a.ln[0] / slices) + 1) & ~1;  // even: the passes walk pixel pairs
+        s.n_valid = a.ln[L];
+        const int per = ((a.ln[L] / slices) + 1) & ~1;  // even: the passes walk pixel pairs
         s.px_begin = slice * per;
-        s.px_end = (slice == slices - 1) ? a.ln[0] : min(a.ln[0], (slice + 1) * per);
+        s.px_end = (slice == slices - 1) ? a.ln[L] : min(a.ln[L], (slice + 1) * per);
     }
     if (tid < SF_NC) s.lab_sum[tid] = 0;
     __syncthreads();
     for (int r = 0; r < reps; r++) {
-        if (WHICH == 1)
-            irls_pass1<VAR>(a, b, 0, s, tid);
-        else
-            irls_pass2<VAR>(a, b, 0, s, tid);
-        __syncthreads();
+        if (WHICH != 2) {
+            irls_pass1<VAR>(a, b, L, s, tid);
+            __syncthreads();
+        }
+        if (WHICH != 1) {
+            irls_pass2<VAR, WHICH == 4>(a, b, L, s, tid);
+            __syncthreads();
+        }
     }
 }
 

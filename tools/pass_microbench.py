@@ -12,6 +12,9 @@ ap.add_argument("--batch", type=int, default=512)
 ap.add_argument("--workload", default="static")
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--slices", type=int, default=1, help="workgroups per stream (experiment: records resident in the Infinity Cache)")
+ap.add_argument("--serpentine", action="store_true", help="pass 1 then pass 2 back to back over the same records, pass 2 upwards against "
+                "pass 2 back down from where pass 1 ended (the solver's order), at levels 0 and 1; alternating, --rounds times")
+ap.add_argument("--rounds", type=int, default=5)
 a = ap.parse_args()
 api = sf.load()
 p = bench.make_params(api, a.workload)
@@ -21,7 +24,24 @@ for b in range(a.batch):
     s.set_current(b, *pairs[b % 8]["new"]); s.set_prediction(b, *pairs[b % 8]["old"])
 s.process_frame(0); s.synchronize()
 npx = 240 * 320
-for which in (1, 2):
+if a.serpentine:
+    # which 3 = both passes upwards, 4 = pass 2 back down; | (L << 4): level L's pixel count and geometry (sf.h: sf_microbench_pass)
+    bpp = 29.0 if p.segmentation_enabled else 28.0
+    for L in (0, 1):
+        px = 2 * a.batch * a.reps * (npx >> (2 * L))  # two passes per repetition
+        for which in (3, 4):
+            s.microbench_pass(which | (L << 4), a.slices << 8, 2)
+        ms = {3: [], 4: []}
+        for r in range(a.rounds):
+            for which in ((3, 4) if r % 2 == 0 else (4, 3)):  # alternate who goes first
+                ms[which].append(s.microbench_pass(which | (L << 4), a.slices << 8, a.reps))
+        for which, name in ((3, "forward "), (4, "serpentine")):
+            v = ms[which]
+            print("level %d %-10s pass 1 + pass 2 x %d: ms per launch %s  mean %.3f  streamed(%d B/px) %7.1f GB/s" % (
+                L, name, a.reps, " ".join("%.3f" % x for x in v), sum(v) / len(v), bpp, bpp * px / (sum(v) / len(v)) / 1e6))
+        ratios = [y / x for x, y in zip(ms[3], ms[4])]
+        print("level %d serpentine / forward time: mean %.4f  per round: %s" % (L, sum(ms[4]) / sum(ms[3]), " ".join("%.4f" % x for x in ratios)))
+for which in (() if a.serpentine else (1, 2)):
     for variant, name in ((0, "product"), (1, "loads only"), (2, "no accumulation")):
         s.microbench_pass(which, variant | (a.slices << 8), 2)
         ms = s.microbench_pass(which, variant | (a.slices << 8), a.reps)
