@@ -166,6 +166,17 @@ int SF_FN(get_variant)(const sf_handle *h, int *variant, int *threads, int *work
  * the pure-odometry configuration, 5 per CU at <= 96 registers for the full solver (segmentation_enabled) -- and picks per
  * launch; everything else has one answer. The CPU oracle reports 1 / 1. Any pointer may be NULL. */
 int SF_FN(get_resident_workgroups)(const sf_handle *h, int *per_cu, int *total);
+/* Environment variables the MI355X library reads PER LAUNCH (test and A/B support; none changes a result beyond what is said
+ * here, the CPU oracle ignores them):
+ *   SF_SOLVER_FORWARD=1        IRLS pass 2 walks its records upwards like pass 1 instead of back down (the order of one fp64
+ *                              sum, ||res||^2, changes; everything that steers the iteration keeps its bits).
+ *   SF_PASS_WINDOW_PX=<pixels> the load policy of the IRLS passes: the last <pixels> pixels of every sweep (rounded up to whole
+ *                              trips of the workgroup) are loaded with the default cache policy, everything before them
+ *                              non-temporally. 0: every record non-temporal. Unset: the library derives the window from its
+ *                              cache budget, the resident workgroups of the launch (sf_get_resident_workgroups) and the 28
+ *                              bytes a pass streams per pixel. Results are bit-identical for every value.
+ *   SF_PASS_POLICY=default     every load of the passes with the default policy (as if the window covered every level);
+ *                              takes precedence over SF_PASS_WINDOW_PX. */
 void SF_FN(destroy)(sf_handle *h);
 int SF_FN(set_params)(sf_handle *h, const sf_params *p);
 int SF_FN(get_params)(const sf_handle *h, sf_params *p);

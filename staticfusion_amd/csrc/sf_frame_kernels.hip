@@ -40,7 +40,7 @@ union FrameShared {
 };
 
 // the stage sequence of one stream; cs says whether this workgroup works alone or as one of a cluster (sf_cluster.h)
-__device__ __forceinline__ void run_stages(const KArgs &a, int b, int stage_mask, int im_count, LDS FrameShared &sh, LDS ClusterShared &cs, int tid) {
+__device__ __forceinline__ void run_stages(const KArgs &a, int b, int stage_mask, int im_count, int pass_window_px, LDS FrameShared &sh, LDS ClusterShared &cs, int tid) {
     long long t0 = 0, t1 = 0;
     long long *prof = a.state[b].prof;
     const bool writer = cl_writer(cs);
@@ -73,7 +73,7 @@ __device__ __forceinline__ void run_stages(const KArgs &a, int b, int stage_mask
         cluster_barrier(cs, tid);  // the labels of every level are visible to every workgroup of the cluster
     }
     if (stage_mask & ST_SOLVE) {
-        stage_solve(a, b, (stage_mask & ST_SOLVER_FORWARD) != 0, *(LDS SolveShared *)&sh.sv, cs, tid);
+        stage_solve(a, b, (stage_mask & ST_SOLVER_FORWARD) != 0, pass_window_px, *(LDS SolveShared *)&sh.sv, cs, tid);
         t0 = wall_clock64();
     }
     // the frame loop pushes the current images into the ring slot the residual stage has just read (im_count % 5 both):
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(SF_NT, SF_OCC) void sf_frame_kernel(const KArgs *__
             }
         }
         cluster_init(*(LDS ClusterShared *)&cs, tid, 1, 0, b, b, nullptr, 0);  // this workgroup alone, on the stream's own slot
-        run_stages(a, b, mask, fl.im_count + k, *(LDS FrameShared *)&sh, *(LDS ClusterShared *)&cs, tid);
+        run_stages(a, b, mask, fl.im_count + k, fl.pass_window_px, *(LDS FrameShared *)&sh, *(LDS ClusterShared *)&cs, tid);
         if (fl.frame_done) {
             if (fl.traj && tid < 16) fl.traj[((size_t)k * a.batch + b) * 16 + tid] = a.state[b].T[tid];
             if (k == fl.n_frames - 1) {
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(SF_NT, SF_OCC) void sf_frame_kernel(const KArgs *__
     }
     cluster_init(*(LDS ClusterShared *)&cs, tid, G, rank, b, a.batch + b * G + rank, (gu64 *)a.sync + (size_t)b * 2 * G * SF_SYNC_WORDS,
                  st.sync_epoch, G > 1 ? &st.sync_failed : nullptr, a.sync_spin_limit);
-    run_stages(a, b, stage_mask, im_count, *(LDS FrameShared *)&sh, *(LDS ClusterShared *)&cs, tid);
+    run_stages(a, b, stage_mask, im_count, fl.pass_window_px, *(LDS FrameShared *)&sh, *(LDS ClusterShared *)&cs, tid);
     // the epoch carries over to the next launch (every workgroup counted the same rendezvous)
     __syncthreads();
     if (tid == 0 && rank == 0) {
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(SF_NT, SF_OCC) void sf_frame_kernel(const KArgs *__
 
 // the IRLS passes alone (measurement support; never part of a solve)
 #ifndef SF_CLUSTER
-__global__ __launch_bounds__(SF_NT, 4) void sf_irls_pass_kernel(const KArgs *__restrict__ ka, int which, int variant, int reps, int slices) {
+__global__ __launch_bounds__(SF_NT, 4) void sf_irls_pass_kernel(const KArgs *__restrict__ ka, int which, int variant, int reps, int slices, int window_px) {
     __shared__ FrameShared sh;
     __shared__ int s_next;
     const KArgs &a = *ka;
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(SF_NT, 4) void sf_irls_pass_kernel(const KArgs *__r
         LDS SolveShared &sv = *(LDS SolveShared *)&sh.sv;
         const int L = which >> 4;  // bits 4.. of `which`: the level whose size and geometry the passes walk (sf_solver_support.h)
 #define SF_MB_CASE(W, V) \
-    if ((which & 15) == W && variant == V) microbench_pass<W, V>(a, b, L, slice, slices, reps, sv, tid)
+    if ((which & 15) == W && variant == V) microbench_pass<W, V>(a, b, L, slice, slices, reps, window_px, sv, tid)
         SF_MB_CASE(1, 0); SF_MB_CASE(1, 1); SF_MB_CASE(1, 2);
         SF_MB_CASE(2, 0); SF_MB_CASE(2, 1); SF_MB_CASE(2, 2);
         SF_MB_CASE(3, 0); SF_MB_CASE(3, 1); SF_MB_CASE(3, 2);  // pass 1 then pass 2, both upwards
@@ -387,9 +387,9 @@ extern "C" __attribute__((visibility("hidden"))) void SF_VARIANT_FN(sf_launch_de
 extern "C" __attribute__((visibility("hidden"))) void SF_VARIANT_FN(sf_launch_frame)(int grid, hipStream_t st, const KArgs *ka, const FrameLaunch *fl) {
     hipLaunchKernelGGL(sf_frame_kernel, dim3(grid), dim3(SF_NT), 0, st, ka, *fl);
 }
-extern "C" __attribute__((visibility("hidden"))) void SF_VARIANT_FN(sf_launch_irls_pass)(int grid, hipStream_t st, const KArgs *ka, int which, int variant, int reps, int slices) {
+extern "C" __attribute__((visibility("hidden"))) void SF_VARIANT_FN(sf_launch_irls_pass)(int grid, hipStream_t st, const KArgs *ka, int which, int variant, int reps, int slices, int window_px) {
 #ifndef SF_CLUSTER
-    hipLaunchKernelGGL(sf_irls_pass_kernel, dim3(grid), dim3(SF_NT), 0, st, ka, which, variant, reps, slices);
+    hipLaunchKernelGGL(sf_irls_pass_kernel, dim3(grid), dim3(SF_NT), 0, st, ka, which, variant, reps, slices, window_px);
 #endif
 }
 // bit 0: this object is a reference-order build (sf_reforder.h): the host allocates its source lists and refuses the cluster variant;

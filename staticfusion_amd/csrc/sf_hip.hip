@@ -13,7 +13,7 @@
 // what every frame object defines under its variant tag (sf_frame_kernels.hip: SF_VARIANT_FN; the tags: csrc/Makefile)
 #define SF_DECLARE_VARIANT(tag)                                                                                  \
     extern "C" SF_INTERNAL void sf_launch_frame_nt##tag(int, hipStream_t, const KArgs *, const FrameLaunch *);    \
-    extern "C" SF_INTERNAL void sf_launch_irls_pass_nt##tag(int, hipStream_t, const KArgs *, int, int, int, int); \
+    extern "C" SF_INTERNAL void sf_launch_irls_pass_nt##tag(int, hipStream_t, const KArgs *, int, int, int, int, int); \
     extern "C" SF_INTERNAL void sf_launch_debug_rows_nt##tag(int, hipStream_t, const KArgs *, int, float *);      \
     extern "C" SF_INTERNAL void sf_variant_geometry_nt##tag(int *, int *);                                        \
     extern "C" SF_INTERNAL int sf_variant_flags_nt##tag(void);
@@ -96,6 +96,20 @@ bool use_five_per_cu(const sf_handle *h) {
     return h->k.p.segmentation_enabled != 0;
 }
 
+// The window of the IRLS sweeps (sf_irls.h: pass_division): how many pixels at the end of a sweep are loaded to stay in the
+// memory-side cache for the pass that follows; the rest of the sweep is loaded non-temporally. One measured constant, the bytes
+// of that cache the windows of all resident workgroups may fill together, over the workgroups of the launch
+// and the 28 bytes a pass streams per pixel. A launch of few workgroups gets a window larger than any level: all default.
+// Test and A/B support, read per launch: SF_PASS_WINDOW_PX=<pixels> overrides the window (0: every load non-temporal),
+// SF_PASS_POLICY=default loads everything with the default policy (include/sf.h).
+static const long long SF_PASS_WINDOW_BUDGET_BYTES = 384ll << 20;  // 384 KiB per workgroup at 1024 resident: profiles/r08a_ab_pass_window.txt
+int pass_window_px(int resident_workgroups) {
+    const long long whole = 1 << 30;
+    if (const char *v = std::getenv("SF_PASS_POLICY")) if (!std::strcmp(v, "default")) return (int)whole;
+    if (const char *v = std::getenv("SF_PASS_WINDOW_PX")) return (int)std::min<long long>(whole, std::max<long long>(0, std::strtoll(v, nullptr, 10)));
+    return (int)std::min<long long>(whole, SF_PASS_WINDOW_BUDGET_BYTES / std::max(1, resident_workgroups) / 28);
+}
+
 // One launch of the frame kernel: `n_frames` consecutive frames of every stream (1: the per-call API). ml: the per-launch
 // pointers of a multi-frame launch (frame counters, index table, pools, trajectory), or null.
 int launch(sf_handle *h, int mask, int im_count, int n_frames, const FrameLaunch *ml) {
@@ -124,6 +138,7 @@ int launch(sf_handle *h, int mask, int im_count, int n_frames, const FrameLaunch
     fl.im_count = im_count;
     fl.n_frames = n_frames;
     fl.spin_limit = 1u << 27;
+    fl.pass_window_px = pass_window_px(grid);
     // test support (tests/test_multi_frame.py): frame k of every third stream is given up once its previous frame is done -- the
     // path of a wait that ran into its bound, which nothing else can provoke
     if (const char *v = std::getenv("SF_DEBUG_GIVE_UP_AT_FRAME")) fl.debug_give_up = (int)std::strtol(v, nullptr, 10);

@@ -547,7 +547,7 @@ int sf_microbench_pass(sf_handle *h, int which, int variant, int reps, float *el
     HIP_TRY(hipMemsetAsync(h->k.queue, 0, sizeof(int), h->stream));
     const int grid = std::min(h->k.batch * slices, h->max_blocks);
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    h->fv->launch_irls_pass(grid, h->stream, (const KArgs *)h->d_args, which, variant, reps, slices);
+    h->fv->launch_irls_pass(grid, h->stream, (const KArgs *)h->d_args, which, variant, reps, slices, pass_window_px(grid));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));

@@ -26,7 +26,7 @@ struct FrameVariant {
     const char *name;
     void (*geometry)(int *threads, int *blocks_per_cu);
     void (*launch_frame)(int grid, hipStream_t st, const KArgs *ka, const FrameLaunch *fl);
-    void (*launch_irls_pass)(int grid, hipStream_t st, const KArgs *ka, int which, int variant, int reps, int slices);
+    void (*launch_irls_pass)(int grid, hipStream_t st, const KArgs *ka, int which, int variant, int reps, int slices, int window_px);
     void (*launch_debug_rows)(int grid, hipStream_t st, const KArgs *ka, int b, float *out);
 };
 
@@ -146,6 +146,7 @@ static int dev_grow(sf_handle *h, T **p, size_t *capacity, size_t count) {
 // shared between the parts (defined in the file named)
 SF_INTERNAL int launch(sf_handle *h, int mask, int im_count, int n_frames = 1, const FrameLaunch *ml = nullptr);  // sf_hip.hip
 SF_INTERNAL int solve_mask(const sf_handle *h, int create_image_pyr);                                            // sf_hip.hip
+SF_INTERNAL int pass_window_px(int resident_workgroups);                                                          // sf_hip.hip
 SF_INTERNAL bool use_five_per_cu(const sf_handle *h);                                                           // sf_hip.hip
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip

@@ -197,35 +197,53 @@ __device__ __forceinline__ void p1_flush(float (&acc)[27], LDS SolveShared &s, i
     for (int q = 0; q < 27; q++) acc[q] = 0.f;
 }
 
-template <int VAR>
-__device__ __noinline__ void irls_pass1(const KArgs &a, int b, int L, LDS SolveShared &s, int tid) {
-    const IrlsCtx c = make_irls_ctx(a, b, L, s);
-    const int lane = tid & 63, wave = tid >> 6;
-    const float inv_c_Cauchy = 1.f / (a.p.kc_Cauchy * uniform_f(s.aver_res));
-#if SF_P1_FOLD
-    const float fold_kc = c.g.inv_max_c * c.g.kph, fold_kd = c.g.inv_max_d;                    // pre-weight = k rsq(a)
-    const float fold_gc = fold_kc * inv_c_Cauchy, fold_gd = fold_kd * inv_c_Cauchy;
-#endif
-    float acc[27];
-#pragma unroll
-    for (int q = 0; q < 27; q++) acc[q] = 0.f;
-    const int set = tid / P1_GROUP;
-    const bool leader = (tid % P1_GROUP) == 0;
-    if (lane < P1_SETS_PER_WAVE) {  // this wave's sets (nobody else touches them: no barrier, LDS operations of a wave are ordered)
-#pragma unroll
-        for (int q = 0; q < 27; q++) s.p1[q][wave * P1_SETS_PER_WAVE + lane] = 0.0;
+// The load policy of a sweep, per trip. A sweep of a pass over [begin, n) is `trips` trips of SF_NT pixel
+// pairs. The records of the last trips it walks -- window_px pixels, rounded up to whole trips -- are what the next pass starts on
+// (serpentine order, solve_irls): they are loaded with the default policy and stay in the memory-side cache. Everything before
+// them will not be read again until the cache has turned over many times: those trips are loaded non-temporally, so that they do
+// not evict the windows of the other workgroups. The policy belongs to the trip whose record is LOADED: trip t issues the load of
+// trip t + 1. window_px = 0: every record nt; window_px >= the range: every load default (what the passes did before there was a
+// policy). The compiler merges the two arms of a branch between an nt and a plain load of one address and drops the nt bit, so a
+// sweep is two instances of its loop, one per policy, entered one after the other with the same running state: the visiting order,
+// the trip counts and the order of every sum are those of one loop.
+//   nt_first: the record of trip 0 is loaded nt;  nt_next: trips [0, nt_next) load their successor's record nt
+__device__ __forceinline__ void pass_division(int begin, int n, int window_px, bool &nt_first, int &nt_next) {
+    const int trips = (((n - begin + 1) >> 1) + SF_NT - 1) / SF_NT;
+    const int wtrips = (int)min((unsigned)trips, ((unsigned)max(window_px, 0) + (SF_NT * 2 - 1)) / (unsigned)(SF_NT * 2));
+    const int split = trips - wtrips;  // trips [0, split) are loaded nt, [split, trips) with the default policy
+    nt_first = split > 0;
+    nt_next = (split >= trips) ? trips : max(split - 1, 0);
+}
+
+// the record of a sweep's first trip, with the sweep's first policy. The empty asm statements keep the two arms apart: the compiler
+// otherwise hoists the loads out of the branch as ONE plain load (the nt bit is metadata it drops when it merges instructions).
+// The wait that follows is where the loops expect the record: with it in front of them, the only waits inside a loop are those
+// for the record it loads itself (vmcnt(2) / vmcnt(0) at the end of a trip).
+#define SF_WAIT_VMCNT0 0x0F70  // s_waitcnt vmcnt(0), the other counters at their maximum (gfx9 encoding)
+__device__ __forceinline__ void load_first_rec(const RecPtrs &rp, int idx0, bool nt, RecVec<2> &r) {
+    if (nt) {
+        asm volatile("" ::: "memory");
+        load_rec<2, true>(rp, idx0, r);
+        asm volatile("" ::: "memory");
+    } else {
+        load_rec<2, false>(rp, idx0, r);
     }
+}
+
+// what the trips of pass 1 read and never change
+struct P1Consts {
+    float inv_c_Cauchy, fold_kc, fold_kd, fold_gc, fold_gd;
     float Vr[6];
-#pragma unroll
-    for (int q = 0; q < 6; q++) Vr[q] = uniform_f(s.Var[q]);
-    const int last = (c.n - 2) & ~1;  // the prefetch past the end re-reads the last pair instead of branching
-    RecVec<2> rv, nx;
-    // the trip count is the WAVE's (its first lane's): every lane stays active to the end, so that the group sums of a
-    // flush see all their lanes; a lane past the end re-reads the last pair with weight 0
-    load_rec<2>(c.rp, min(c.begin + tid * 2, last), rv);
-    int since = 0;
-    for (int i0 = c.begin + tid * 2, iw = uniform_i(c.begin + (tid - lane) * 2); iw < c.n; i0 += SF_NT * 2, iw += SF_NT * 2) {
-        load_rec<2>(c.rp, min(i0 + SF_NT * 2, last), nx);
+    int last, set;
+    bool leader;
+};
+// the trips of pass 1 from (i0, iw) until the wave's iw reaches iw_end; NT: the policy of the record each trip loads (the next one's)
+template <int VAR, bool NT>
+__device__ __forceinline__ void p1_trips(const IrlsCtx &c, LDS SolveShared &s, const P1Consts &k, int iw_end, int &i0, int &iw, RecVec<2> &rv,
+                                         float (&acc)[27], int &since) {
+    RecVec<2> nx;
+    for (; iw < iw_end; i0 += SF_NT * 2, iw += SF_NT * 2) {
+        load_rec<2, NT>(c.rp, min(i0 + SF_NT * 2, k.last), nx);
         const bool in = i0 < c.n;
         const bool ok0 = sanitize<2>(rv, 0) && in, ok1 = sanitize<2>(rv, 1) && in;
         if constexpr (VAR == 1) {
@@ -238,7 +256,7 @@ __device__ __noinline__ void irls_pass1(const KArgs &a, int b, int L, LDS SolveS
         }
         float bseg0 = s.b_segm[rv.lab[0]], bseg1 = s.b_segm[rv.lab[1]];  // invalid pixels carry label 0 after sanitize()
         float fu0, fv0;
-        split_index(c.g, min(i0, last), fu0, fv0);
+        split_index(c.g, min(i0, k.last), fu0, fv0);
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const bool ok = j ? ok1 : ok0;
@@ -260,18 +278,18 @@ __device__ __noinline__ void irls_pass1(const KArgs &a, int b, int L, LDS SolveS
             if (j == 0) asm volatile("" : "+v"(bseg0), "+v"(bseg1));  // LDS reads stay unconditional, landed by now
             const float b_weight = ok ? std_max(0.f, std_min(1.f, j ? bseg1 : bseg0)) : 0.f;
             float raw_c, raw_d;
-            fact_residuals<float>(p, Vr, raw_c, raw_d);
-            const float uc = raw_c * fold_gc, ud = raw_d * fold_gd;
-            const float w_c = (b_weight * fold_kc) * vrsq(fmaf(uc, uc, p.ac));
-            const float w_d = (b_weight * fold_kd) * vrsq(fmaf(ud, ud, p.ad));
+            fact_residuals<float>(p, k.Vr, raw_c, raw_d);
+            const float uc = raw_c * k.fold_gc, ud = raw_d * k.fold_gd;
+            const float w_c = (b_weight * k.fold_kc) * vrsq(fmaf(uc, uc, p.ac));
+            const float w_d = (b_weight * k.fold_kd) * vrsq(fmaf(ud, ud, p.ad));
 #else
             fact_from_record<float>(c.g, fu, fv, rv.dn[j], rv.v[R_DW][j], rv.v[R_DCU][j], rv.v[R_DCV][j], rv.v[R_DCT][j],
                                     rv.v[R_DDU][j], rv.v[R_DDV][j], p);
             if (j == 0) asm volatile("" : "+v"(bseg0), "+v"(bseg1));  // LDS reads stay unconditional, landed by now
             const float b_weight = ok ? std_max(0.f, std_min(1.f, j ? bseg1 : bseg0)) : 0.f;
             float res_c, res_d;
-            fact_residuals<float>(p, Vr, res_c, res_d);
-            const float tc = res_c * inv_c_Cauchy, td = res_d * inv_c_Cauchy;
+            fact_residuals<float>(p, k.Vr, res_c, res_d);
+            const float tc = res_c * k.inv_c_Cauchy, td = res_d * k.inv_c_Cauchy;
 #if SF_FAST_WEIGHTS
             const float w_c = b_weight * vrsq(vfma(tc, tc, 1.f));
             const float w_d = b_weight * vrsq(vfma(td, td, 1.f));
@@ -314,11 +332,47 @@ __device__ __noinline__ void irls_pass1(const KArgs &a, int b, int L, LDS SolveS
         if constexpr (VAR == 0) {
             if (++since == SF_P1_FLUSH) {  // uniform: every lane of the wave has made the same number of trips
                 since = 0;
-                p1_flush(acc, s, set, leader);
+                p1_flush(acc, s, k.set, k.leader);
             }
         }
     }
-    p1_flush(acc, s, set, leader);
+}
+
+template <int VAR>
+__device__ __noinline__ void irls_pass1(const KArgs &a, int b, int L, int window_px, LDS SolveShared &s, int tid) {
+    const IrlsCtx c = make_irls_ctx(a, b, L, s);
+    const int lane = tid & 63, wave = tid >> 6;
+    P1Consts k;
+    k.inv_c_Cauchy = 1.f / (a.p.kc_Cauchy * uniform_f(s.aver_res));
+#if SF_P1_FOLD
+    k.fold_kc = c.g.inv_max_c * c.g.kph, k.fold_kd = c.g.inv_max_d;                              // pre-weight = k rsq(a)
+    k.fold_gc = k.fold_kc * k.inv_c_Cauchy, k.fold_gd = k.fold_kd * k.inv_c_Cauchy;
+#endif
+    float acc[27];
+#pragma unroll
+    for (int q = 0; q < 27; q++) acc[q] = 0.f;
+    k.set = tid / P1_GROUP;
+    k.leader = (tid % P1_GROUP) == 0;
+    if (lane < P1_SETS_PER_WAVE) {  // this wave's sets (nobody else touches them: no barrier, LDS operations of a wave are ordered)
+#pragma unroll
+        for (int q = 0; q < 27; q++) s.p1[q][wave * P1_SETS_PER_WAVE + lane] = 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++) k.Vr[q] = uniform_f(s.Var[q]);
+    k.last = (c.n - 2) & ~1;  // the prefetch past the end re-reads the last pair instead of branching
+    bool nt_first;
+    int nt_next;
+    pass_division(c.begin, c.n, window_px, nt_first, nt_next);
+    RecVec<2> rv;
+    // the trip count is the WAVE's (its first lane's): every lane stays active to the end, so that the group sums of a
+    // flush see all their lanes; a lane past the end re-reads the last pair with weight 0
+    load_first_rec(c.rp, min(c.begin + tid * 2, k.last), nt_first, rv);
+    __builtin_amdgcn_s_waitcnt(SF_WAIT_VMCNT0);
+    int since = 0;  // (the flush cadence runs through both loop instances)
+    int i0 = c.begin + tid * 2, iw = uniform_i(c.begin + (tid - lane) * 2);
+    p1_trips<VAR, true>(c, s, k, min(c.n, iw + nt_next * (SF_NT * 2)), i0, iw, rv, acc, since);
+    p1_trips<VAR, false>(c, s, k, c.n, i0, iw, rv, acc, since);
+    p1_flush(acc, s, k.set, k.leader);
     // this wave's sets, in order -> s.red[wave][0..26]
     __builtin_amdgcn_wave_barrier();
     if (lane < 27) {
@@ -410,25 +464,15 @@ __device__ __forceinline__ unsigned long long to_fix32_pos(float x) {
 // the last SF_NT pairs, i0 falls by SF_NT * 2 per trip, lanes keep ascending addresses inside a trip), so that the pass starts
 // on the records pass 1 has just read and ends at `begin`, where the next pass 1 starts. The per-label
 // sums are integers: the same bits in either direction; sq changes the order of its fp64 sum only.
-template <int VAR, int DIR = 0>
-__device__ __noinline__ void irls_pass2(const KArgs &a, int b, int L, LDS SolveShared &s, int tid) {
-    const IrlsCtx c = make_irls_ctx(a, b, L, s);
-    const int lane = tid & 63, wave = tid >> 6;
-    float Vr[6];
-#pragma unroll
-    for (int q = 0; q < 6; q++) Vr[q] = uniform_f(s.Var[q]);
-    double sq = 0.0;
-    int cur_lab = 0;
-    unsigned long long cur_sum = 0;
-    const int last = (c.n - 2) & ~1;
-    // DIR 1: the pair of lane 0 in the first trip lies SF_NT pairs below the end of the range (below `begin` in a range of fewer
-    // pairs: those lanes make no trip); begin is even, so every pair starts where a pair of the upward walk starts
+// the trips of pass 2 from i0 until it passes `stop` (DIR 0: i0 < stop; DIR 1: i0 >= stop); NT: the policy of the record each trip
+// loads (the next one's)
+template <int VAR, int DIR, bool NT>
+__device__ __forceinline__ void p2_trips(const IrlsCtx &c, LDS SolveShared &s, const float (&Vr)[6], int last, int stop, int &i0, RecVec<2> &rv,
+                                         double &sq, int &cur_lab, unsigned long long &cur_sum) {
     const int step = DIR ? -SF_NT * 2 : SF_NT * 2;
-    const int start = (DIR ? c.begin + ((c.n - c.begin + 1) & ~1) - SF_NT * 2 : c.begin) + tid * 2;
-    RecVec<2> rv, nx;
-    if (DIR ? start >= c.begin : start < c.n) load_rec<2>(c.rp, start, rv);
-    for (int i0 = start; DIR ? i0 >= c.begin : i0 < c.n; i0 += step) {
-        load_rec<2>(c.rp, DIR ? max(i0 + step, c.begin) : min(i0 + step, last), nx);  // next pair in flight during this one
+    RecVec<2> nx;
+    for (; DIR ? i0 >= stop : i0 < stop; i0 += step) {
+        load_rec<2, NT>(c.rp, DIR ? max(i0 + step, c.begin) : min(i0 + step, last), nx);  // next pair in flight during this one
         const bool ok0 = sanitize<2>(rv, 0), ok1 = sanitize<2>(rv, 1);
         if constexpr (VAR == 1) {
             float t = rv.dn[0] + rv.dn[1];
@@ -473,6 +517,34 @@ __device__ __noinline__ void irls_pass2(const KArgs &a, int b, int L, LDS SolveS
         }
         rv = nx;
     }
+}
+
+template <int VAR, int DIR = 0>
+__device__ __noinline__ void irls_pass2(const KArgs &a, int b, int L, int window_px, LDS SolveShared &s, int tid) {
+    const IrlsCtx c = make_irls_ctx(a, b, L, s);
+    const int lane = tid & 63, wave = tid >> 6;
+    float Vr[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) Vr[q] = uniform_f(s.Var[q]);
+    double sq = 0.0;
+    int cur_lab = 0;
+    unsigned long long cur_sum = 0;
+    const int last = (c.n - 2) & ~1;
+    // DIR 1: the pair of lane 0 in the first trip lies SF_NT pairs below the end of the range (below `begin` in a range of fewer
+    // pairs: those lanes make no trip); begin is even, so every pair starts where a pair of the upward walk starts
+    const int step = DIR ? -SF_NT * 2 : SF_NT * 2;
+    const int start = (DIR ? c.begin + ((c.n - c.begin + 1) & ~1) - SF_NT * 2 : c.begin) + tid * 2;
+    // the window is where the sweep ENDS: the top of the range for the upward walk, [begin, begin + window) for the walk back down
+    bool nt_first;
+    int nt_next;
+    pass_division(c.begin, c.n, window_px, nt_first, nt_next);
+    RecVec<2> rv;
+    if (DIR ? start >= c.begin : start < c.n) load_first_rec(c.rp, start, nt_first, rv);
+    __builtin_amdgcn_s_waitcnt(SF_WAIT_VMCNT0);
+    int i0 = start;
+    p2_trips<VAR, DIR, true>(c, s, Vr, last, DIR ? max(c.begin, start + nt_next * step + 1) : min(c.n, start + nt_next * step), i0, rv, sq, cur_lab,
+                             cur_sum);
+    p2_trips<VAR, DIR, false>(c, s, Vr, last, DIR ? c.begin : c.n, i0, rv, sq, cur_lab, cur_sum);
     if (cur_sum) lds_add(&s.lab_sum[cur_lab], (long long)cur_sum);
     sq = wave_sum_f64(sq);
     if (lane == 0) s.red[wave][27] = sq;
@@ -556,7 +628,7 @@ __device__ __noinline__ void irls_iteration_tail(const KArgs &a, LDS SolveShared
     }
 }
 
-__device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level, int kouter, bool forward, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
+__device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level, int kouter, bool forward, int window_px, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     const bool seg = a.p.segmentation_enabled != 0;
     const int N = __builtin_amdgcn_readfirstlane(s.n_valid);
@@ -624,7 +696,7 @@ __device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level,
 #if SF_REFORDER
         ro_pass1(a, b, L, s, tid);
 #else
-        irls_pass1<0>(a, b, L, s, tid);
+        irls_pass1<0>(a, b, L, window_px, s, tid);
 #endif
         __syncthreads();
         irls_reduce_normal(s, cs, tid);
@@ -636,11 +708,12 @@ __device__ __noinline__ void solve_irls(const KArgs &a, int b, int L, int level,
         ro_pass2(a, b, L, s, tid);
 #else
         // serpentine: pass 1 ends at the top of the records, pass 2 starts there and ends where the next pass 1 starts, so each
-        // pass begins on the lines its predecessor touched last (uniform branch; `forward` is the old order, for tests and A/B)
+        // pass begins on the lines its predecessor touched last (uniform branch; `forward` is the old order, for tests and A/B).
+        // window_px (uniform, from the launch): only that many pixels at the end of each sweep are loaded to stay cached (pass_division)
         if (forward)
-            irls_pass2<0, 0>(a, b, L, s, tid);
+            irls_pass2<0, 0>(a, b, L, window_px, s, tid);
         else
-            irls_pass2<0, 1>(a, b, L, s, tid);
+            irls_pass2<0, 1>(a, b, L, window_px, s, tid);
 #endif
         __syncthreads();
         irls_reduce_residuals(s, cs, tid);

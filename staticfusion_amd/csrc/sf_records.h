@@ -23,35 +23,45 @@ struct RecPtrs {
 // base (uniform, SGPR pair) + 32-bit unsigned byte offset (one VGPR shared by all planes): the
 // saddr + voffset form of global_load, no 64-bit per-plane address arithmetic in the loop
 typedef __attribute__((address_space(1))) const char gcchar;
-template <int VEC>
+// NT: the load policy, a compile-time property of the load. false: the default policy (the line is kept in L2 and in the
+// memory-side cache); true: non-temporal (global_load ... nt, the same address form): for bytes nobody reads again before
+// the caches have turned over, so that they do not displace the lines somebody will (the passes: sf_irls.h, pass_division)
+template <bool NT, class V, class P>
+__device__ __forceinline__ V load_policy(P *q) {
+    if constexpr (NT)
+        return __builtin_nontemporal_load(q);
+    else
+        return *q;
+}
+template <int VEC, bool NT = false>
 __device__ __forceinline__ void load_plane(gcfloat *p, int idx0, float (&out)[VEC]) {
     const unsigned boff = (unsigned)idx0 * 4u;
     gcchar *q = (gcchar *)p + boff;
     if constexpr (VEC == 1) {
-        out[0] = *(gcfloat *)q;
+        out[0] = load_policy<NT, float>((gcfloat *)q);
     } else if constexpr (VEC == 2) {
-        const vfloat2 v = *(gcfloat2 *)q;
+        const vfloat2 v = load_policy<NT, vfloat2>((gcfloat2 *)q);
         out[0] = v.x;
         out[1] = v.y;
     } else {
-        const vfloat4 v = *(gcfloat4 *)q;
+        const vfloat4 v = load_policy<NT, vfloat4>((gcfloat4 *)q);
         out[0] = v.x;
         out[1] = v.y;
         out[2] = v.z;
         out[3] = v.w;
     }
 }
-template <int VEC>
+template <int VEC, bool NT = false>
 __device__ __forceinline__ void load_labels(gcu8 *p, int idx0, int (&out)[VEC]) {
     gcchar *q = (gcchar *)p + (unsigned)idx0;
     if constexpr (VEC == 1) {
-        out[0] = *(gcu8 *)q;
+        out[0] = load_policy<NT, uint8_t>((gcu8 *)q);
     } else if constexpr (VEC == 2) {
-        const unsigned v = *(gcu16 *)q;
+        const unsigned v = load_policy<NT, unsigned short>((gcu16 *)q);
         out[0] = v & 255u;
         out[1] = v >> 8;
     } else {
-        const unsigned v = *(gcu32 *)q;
+        const unsigned v = load_policy<NT, unsigned>((gcu32 *)q);
         out[0] = v & 255u;
         out[1] = (v >> 8) & 255u;
         out[2] = (v >> 16) & 255u;
@@ -66,18 +76,19 @@ struct RecVec {
     unsigned labraw;  // the VEC label bytes as loaded; unpacked at the point of use (rec_label)
     int lab[VEC];
 };
-template <int VEC>
+// (the record planes, the new-depth plane and the label plane of a record share one policy)
+template <int VEC, bool NT = false>
 __device__ __forceinline__ void load_rec(const RecPtrs &rp, int idx0, RecVec<VEC> &r) {
     static_assert(VEC == 2, "the passes walk pixel pairs");
     // uniform: without segmentation every valid pixel belongs to cluster 0 and the plane is not read. The bytes are kept
     // as loaded: unpacking them here, inside the branch, made the compiler wait for the load (s_waitcnt vmcnt(0)) BEFORE
     // the other seven loads of the record were issued -- two memory round trips per trip of the loop
     unsigned raw = 0;
-    if (rp.with_labels) raw = *(gcu16 *)((gcchar *)rp.lab + (unsigned)idx0);
+    if (rp.with_labels) raw = load_policy<NT, unsigned short>((gcu16 *)((gcchar *)rp.lab + (unsigned)idx0));
     r.labraw = raw;
-    load_plane<VEC>(rp.dnew, idx0, r.dn);
+    load_plane<VEC, NT>(rp.dnew, idx0, r.dn);
 #pragma unroll
-    for (int q = 0; q < R_COUNT; q++) load_plane<VEC>(rp.p[q], idx0, r.v[q]);
+    for (int q = 0; q < R_COUNT; q++) load_plane<VEC, NT>(rp.p[q], idx0, r.v[q]);
 }
 
 // Per-level constants needed to rebuild a pixel's rows from its compact record.

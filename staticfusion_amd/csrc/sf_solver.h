@@ -47,7 +47,8 @@
 #define SF_CLUSTER_SOLO_PIXELS 8192
 
 // forward (uniform, from the launch: ST_SOLVER_FORWARD): pass 2 of the IRLS walks upwards like pass 1 -- tests and A/B only
-__device__ __noinline__ void stage_solve(const KArgs &a, int b, bool forward, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
+// window_px (uniform, FrameLaunch::pass_window_px): the pixels at the end of each IRLS sweep that are loaded to stay cached (sf_irls.h)
+__device__ __noinline__ void stage_solve(const KArgs &a, int b, bool forward, int window_px, LDS SolveShared &s, LDS ClusterShared &cs, int tid) {
     StreamState &st = a.state[b];
     if (tid < 16) s.T[tid] = (tid % 5 == 0) ? 1.f : 0.f;  // T_odometry.setIdentity()  (:1091)
     if (tid < 6) {
@@ -109,7 +110,7 @@ __device__ __noinline__ void stage_solve(const KArgs &a, int b, bool forward, LD
 #endif
 #endif
             PROF_MARK(s, tid, PF_LINEARISE);
-            solve_irls(a, b, L, i, k, forward, s, cs, tid);
+            solve_irls(a, b, L, i, k, forward, window_px, s, cs, tid);
             if (tid == 0) {
                 s.n_outer++;
                 double s2 = 0.0;

@@ -62,10 +62,10 @@ __device__ __forceinline__ void debug_rows(const KArgs &a, int b, float *out, in
 //  WHICH 1 / 2: that pass alone. WHICH 3 / 4: one IRLS iteration's traffic, pass 1 then pass 2 back to back over the same
 //  range, pass 2 upwards (3) or back down (4: the serpentine order of solve_irls). L > 0 walks the first ln[L] pixels of the
 //  same record planes with that level's geometry and depth plane: the values mean nothing there, the bytes and the
-//  instructions are the level's (sanitize() keeps every row finite).
+//  instructions are the level's (sanitize() keeps every row finite). window_px: the load policy of the sweeps, as in a solve.
 // ---------------------------------------------------------------------------------------------
 template <int WHICH, int VAR>
-__device__ void microbench_pass(const KArgs &a, int b, int L, int slice, int slices, int reps, LDS SolveShared &s, int tid) {
+__device__ void microbench_pass(const KArgs &a, int b, int L, int slice, int slices, int reps, int window_px, LDS SolveShared &s, int tid) {
     const StreamState &st = a.state[b];
     if (tid < SF_NC) s.b_segm[tid] = a.p.segmentation_enabled ? st.b_segm[tid] : 1.f;
     if (tid < 6) s.Var[tid] = st.twist_level[tid];
@@ -84,11 +84,11 @@ __device__ void microbench_pass(const KArgs &a, int b, int L, int slice, int sli
     __syncthreads();
     for (int r = 0; r < reps; r++) {
         if (WHICH != 2) {
-            irls_pass1<VAR>(a, b, L, s, tid);
+            irls_pass1<VAR>(a, b, L, window_px, s, tid);
             __syncthreads();
         }
         if (WHICH != 1) {
-            irls_pass2<VAR, WHICH == 4>(a, b, L, s, tid);
+            irls_pass2<VAR, WHICH == 4>(a, b, L, window_px, s, tid);
             __syncthreads();
         }
     }

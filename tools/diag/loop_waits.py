@@ -14,7 +14,7 @@ import exec_lint  # noqa: E402
 
 
 def innermost_loops(lib, kern, fn, verbose=False):
-    """[{valu, loads, stores, flat, scratch, dpp, lds, waits: [vmcnt, ...]}, ...] of function `fn` in build `kern` of `lib`"""
+    """[{valu, loads, nt_loads, stores, flat, scratch, dpp, lds, waits: [vmcnt, ...]}, ...] of function `fn` in build `kern` of `lib`"""
     out = []
     for text in exec_lint.code_objects(lib):
         kernels = re.findall(r"<(_Z\d+sf_frame_kernel\w*)>:", text)
@@ -44,13 +44,14 @@ def innermost_loops(lib, kern, fn, verbose=False):
             seg = lines[a:b]
             count = lambda pred: sum(1 for x in seg if pred(x))
             rec = {"lines": (a, b), "valu": count(lambda x: re.match(r"\s*v_", x) is not None), "loads": count(lambda x: "global_load" in x),
+                   "nt_loads": count(lambda x: "global_load" in x and re.search(r"\bnt\b", x.split("//")[0]) is not None),  # non-temporal policy
                    "stores": count(lambda x: "global_store" in x), "flat": count(lambda x: "flat_" in x), "scratch": count(lambda x: "scratch_" in x),
                    "dpp": count(lambda x: "dpp" in x), "lds": count(lambda x: re.match(r"\s*ds_", x) is not None),
                    "waits": [int(re.search(r"vmcnt\((\d+)\)", x).group(1)) for x in seg if "vmcnt" in x]}
             out.append(rec)
             if verbose:
-                print("  loop at lines %d..%d: VALU %d, global loads %d, global stores %d, flat %d, scratch %d, DPP %d, LDS %d; vmcnt of its waits: %s" % (
-                    a, b, rec["valu"], rec["loads"], rec["stores"], rec["flat"], rec["scratch"], rec["dpp"], rec["lds"], " ".join(map(str, rec["waits"])) or "-"))
+                print("  loop at lines %d..%d: VALU %d, global loads %d (%d nt), global stores %d, flat %d, scratch %d, DPP %d, LDS %d; vmcnt of its waits: %s" % (
+                    a, b, rec["valu"], rec["loads"], rec["nt_loads"], rec["stores"], rec["flat"], rec["scratch"], rec["dpp"], rec["lds"], " ".join(map(str, rec["waits"])) or "-"))
     return out
 
 
