@@ -242,6 +242,7 @@ void sf_destroy(sf_handle *h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     orphan_maps(h);  // maps outliving their handle: their memory is freed now, every later call on them fails cleanly
+    migrate_release(h);
     for (void *p : h->allocs) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -442,18 +443,11 @@ int sf_create_ex(const sf_params *p, int rows, int cols, int batch, int device, 
 
     // constructor state (reference FrontEnd.cpp:79-81,110,152-154)
     std::vector<StreamState> st(B);
-    std::memset(st.data(), 0, B * sizeof(StreamState));
-    for (auto &s : st) {
-        for (int q = 0; q < 16; q++) s.T[q] = (q % 5 == 0) ? 1.f : 0.f;
-        for (int l = 0; l < SF_NC; l++) {
-            s.b_segm[l] = 0.5f;
-            s.conn[l] = 1u << l;
-            s.cluster_res[l] = std::nanf("");
+    for (auto &s : st)  // (sf_host.h: sf_ctor_state_word, shared with sfm_reset_streams)
+        for (size_t o = 0; o < sizeof(StreamState); o += 4) {
+            const uint32_t w = sf_ctor_state_word(o, p->kb);
+            std::memcpy((char *)&s + o, &w, 4);
         }
-        for (int i = 0; i < SF_HISTORY; i++)
-            for (int q = 0; q < 16; q++) s.hist_T[i][q] = (q % 5 == 0) ? 1.f : 0.f;
-        s.kb = p->kb;
-    }
     for (size_t b = 0; b < B; b++) st[b].last_slot = (int32_t)b;
     HIP_OR_FREE(hipMemcpy(k.state, st.data(), B * sizeof(StreamState), hipMemcpyHostToDevice));
     if (!k.cluster_g && (int)B > std::max(h->max_blocks, h->max_blocks_o5)) {

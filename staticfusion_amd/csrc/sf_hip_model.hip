@@ -1,5 +1,6 @@
 // sf_hip_model.hip — libsf_hip.so, the map side of include/sf.h without OpenGL: the
 // frame-to-model prediction (sf_predict.h) and the surfel map -- index images, data association, fusion, cleaning (sf_fusion.h).
+#include "../../include/sf_migrate.h"  // sfm_map_rebind (struct sf_map is local to this file)
 #include "sf_host.h"
 #include "sf_predict.h"
 #include "sf_fusion.h"
@@ -320,6 +321,26 @@ void sf_map_destroy(sf_map *m) {
         map_release(m);
     }  // else: sf_destroy of the handle already released the memory and left the map as an empty shell
     delete m;
+}
+// include/sf_migrate.h: the map follows its stream to another handle. Its memory is its own (map_alloc) and stays where it is;
+// what changes is whose stream orders the work on it and whose sf_destroy releases it.
+int sfm_map_rebind(sf_map *m, sf_handle *dst) {
+    if (!m || !dst) return fail(SF_ERR_ARG, "sfm_map_rebind: null");
+    sf_handle *old = m->h;
+    if (!old) return fail(SF_ERR_ARG, "sfm_map_rebind: the handle this map was created from has been destroyed");
+    if (old == dst) return SF_OK;
+    if (dst->device != old->device) return fail(SF_ERR_ARG, "sfm_map_rebind: the destination handle is on another device");
+    if (dst->k.rows != old->k.rows || dst->k.cols != old->k.cols) return fail(SF_ERR_ARG, "sfm_map_rebind: the destination handle has another resolution");
+    HIP_TRY(hipSetDevice(old->device));
+    HIP_TRY(hipStreamSynchronize(old->stream));  // nothing queued on the old handle still works on the map
+    for (auto it = old->maps.begin(); it != old->maps.end(); ++it)
+        if (*it == m) {
+            old->maps.erase(it);
+            break;
+        }
+    dst->maps.push_back(m);
+    m->h = dst;
+    return SF_OK;
 }
 static void pose_compose(const float *a, const float *b, float *out) {  // Eigen::Matrix4f product, column-major
     float r[16];

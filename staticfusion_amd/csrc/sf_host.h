@@ -4,6 +4,8 @@
 //   sf_hip_solver.hip  images in, frames (one or several per launch), results and debug planes out, measurement support
 //   sf_hip_input.hip   the input stage: loader decimation / RGB -> intensity, bilateral depth filter (sf_input.h)
 //   sf_hip_model.hip   frame-to-model prediction and the surfel map without OpenGL (sf_predict.h, sf_fusion.h)
+//   sf_hip_migrate.hip single streams between handles, to and from host memory, back to constructor state (sf_migrate.h;
+//                      its interface is include/sf_migrate.h, symbols sfm_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,7 +96,39 @@ struct sf_handle {
     int multi_capacity = 0;          // frames the two index buffers hold
     int traj_capacity = 0;           // frames d_traj holds
     int solver_timed_frames = 1;     // frames of the launch evk0 / evk1 bracket
+    // stream migration (sf_hip_migrate.hip): the per-call segment tables, a ring of device + pinned host slots like the one of
+    // sf_advance_sequences_device (a call queues up behind running kernels; a slot is reused after its kernel has executed),
+    // the event the two handles of a copy order their HIP streams with, and the staging block of export / import
+    static const int MIG_SLOTS = 4;
+    void *mig_tab_dev[MIG_SLOTS] = {};
+    void *mig_tab_host[MIG_SLOTS] = {};
+    hipEvent_t mig_done[MIG_SLOTS] = {};
+    unsigned mig_calls = 0;
+    hipEvent_t mig_ev = nullptr;
+    uint8_t *mig_stage = nullptr;
+    size_t mig_stage_bytes = 0;
 };
+
+// Constructor state of a stream (reference FrontEnd.cpp:79-81,110,152-154), as the 32-bit word at byte offset `off` of its
+// StreamState: T_odometry and the pose ring are identity, b_segm 0.5, conn[l] = 1 << l, perClusterAverageResidual NaN, kb the
+// handle's, everything else zero. sf_create_ex fills the whole struct from it; sfm_reset_streams the members that travel.
+__host__ __device__ static inline uint32_t sf_ctor_state_word(size_t off, float kb) {
+    const uint32_t one = 0x3f800000u, half = 0x3f000000u, quiet_nan = 0x7fc00000u;
+    const size_t w = off / 4;
+#define SF_IN(member) (off >= offsetof(StreamState, member) && off < offsetof(StreamState, member) + sizeof(StreamState::member))
+    if (SF_IN(T)) return ((w - offsetof(StreamState, T) / 4) % 5 == 0) ? one : 0u;
+    if (SF_IN(hist_T)) return (((w - offsetof(StreamState, hist_T) / 4) % 16) % 5 == 0) ? one : 0u;
+    if (SF_IN(b_segm)) return half;
+    if (SF_IN(conn)) return 1u << (w - offsetof(StreamState, conn) / 4);
+    if (SF_IN(cluster_res)) return quiet_nan;
+    if (SF_IN(kb)) {
+        union { float f; uint32_t u; } v;
+        v.f = kb;
+        return v.u;
+    }
+#undef SF_IN
+    return 0u;
+}
 
 // the thread's last error text (sf_last_error); returns `code`
 SF_INTERNAL int sf_fail(int code, const std::string &msg);
@@ -153,4 +187,5 @@ SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 //
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
 SF_INTERNAL int input_alloc(sf_handle *h);                                    // sf_hip_input.hip: buffers of the input stage, on first use
 SF_INTERNAL void orphan_maps(sf_handle *h);                                   // sf_hip_model.hip: sf_destroy releases the handle's maps
+SF_INTERNAL void migrate_release(sf_handle *h);                               // sf_hip_migrate.hip: sf_destroy releases the pinned tables and events
 }
