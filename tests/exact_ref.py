@@ -79,7 +79,8 @@ def warp_reference(depth, intensity, xx, yy, T_odometry, tan_half_fovh):
     Returns a dict of (rows, cols) arrays: `w` (exact integer weight sums of the unambiguous sources), `depth`, `intensity` (exact
     quotients), `checked`, the per-cell bound terms `e_depth` (sum w e_d / sum w), `abs_depth` / `abs_intensity` (sum |w v| / sum
     w), `count` (contributions), and scalars: `n_sources`, `n_ambiguous`, `max_depth_w`, `min_depth_w_margin` (min depth_w - e_d),
-    `max_count`. Use `warp_bounds` for the tolerance of a given summation path.
+    `max_count`; `sums` (the raw sums of the unambiguous sources) and `ambiguous` (per ambiguous source: candidate ranges, exact
+    position, warped depth, intensity, e_d) for section E. Use `warp_bounds` for the tolerance of a given summation path.
     """
     rows, cols = depth.shape
     f, disp_u, disp_v = warp_geometry(rows, cols, tan_half_fovh)
@@ -156,6 +157,12 @@ def warp_reference(depth, intensity, xx, yy, T_odometry, tan_half_fovh):
         max_depth_w=float(D.max()) if D.size else 0.0, min_depth_w_margin=float(Dm.min()) if D.size else np.inf,
         min_intensity=float(ii.min()) if ii.size else 0.0, max_intensity=float(ii.max()) if ii.size else 0.0,
         max_count=int(CNT.max()),
+        # for section E, which has to carry the ambiguous sources through a sum instead of leaving their cells out: the raw sums of
+        # the unambiguous sources, and per ambiguous source its candidate centi-pixel ranges, its exact position and its values
+        sums=dict(w=W, depth=SD, intensity=SI, e_depth=SE, count=CNT),
+        ambiguous=dict(u_lo=u_lo[amb].astype(np.int64), u_hi=u_hi[amb].astype(np.int64), v_lo=v_lo[amb].astype(np.int64),
+                       v_hi=v_hi[amb].astype(np.int64), u_exact=np.trunc(Uc[amb]).astype(np.int64), v_exact=np.trunc(Vc[amb]).astype(np.int64),
+                       depth_w=D[amb], intensity=ii[amb], e_depth=e_d[amb]),
     )
 
 
@@ -588,3 +595,275 @@ def seg_prior_reference(d_new, d_warp, labels, kz, behind_camera="product", n_la
              "fp64": np.where(full, me + 2 * U32 * am, z)}
     return dict(size=size, nonnull=nn, lambda_t_w=lam, b_prior=b, bound=bound, starved=starved, full=full, terms=t, term_labels=lab[nonnull],
                 sum=S)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+#  E. computeResidualsAgainstPreviousImage (reference FrontEnd.cpp:896-1069) and buildSegmImage (SegmentationBackground.cpp:
+#     176-197): the five-frame residuals per cluster from the images fed, the poses reported and the labels
+# --------------------------------------------------------------------------------------------------------------------------
+# Counts (u = 2^-24 per float rounding), for a counted target pixel with current depth dc, warped depth dw, intensity
+# difference idiff and warped intensity iw:
+#   dw, iw        the splat of section A: bd, bi = warp_bounds(., ordered) of the path the build takes at level 0
+#   dc - dw       one rounding: u |dc - dw|;   idiff - iw: u |idiff - iw|, times k: one more -> 2 u k |idiff - iw|
+#   t = |.| + k |.|   one rounding (or none, fused): u t
+#   -> e_t = bd + k bi + u (|dc - dw| + 2 k |idiff - iw|) + u t
+#   integer sums (the product builds): t 2^32 is exact in float (a power of two), to_fix truncates it by less than one unit:
+#       2^-32 per term; the int64 sums over lanes, labels and workgroups are exact; (float)(sum 2^-32): u; / float(2 (c + 1)): u
+#       -> (sum e_t + c 2^-32) / (2 (c + 1)) + 2 u |result|
+#   float order (the oracle, the reference-order build): c sequential float additions, gamma_c sum |t|, in place of c 2^-32;
+#       the division u (the 2 u above covers it)
+HISTORY = 5               # bufferLength (StaticFusion-datasets.cpp)
+N_LABELS = 24             # NUM_CLUSTERS; the label of a pixel without a cluster
+FIX_RES_Q = 2.0 ** -32    # resolution of the per-label residual sums (sf_device_common.h: FIX_RES)
+STATIC_RESIDUAL = 0.017   # buildSegmImage's threshold on the mean residual (SegmentationBackground.cpp:187)
+MAX_COMBINATIONS = 4096   # candidate placements of the ambiguous sources of ONE cell that are enumerated
+
+
+def mul4_cm_f32(A, B):
+    """mul4_cm (sf_smallmath.h; reference FrontEnd.cpp:766): C = A B in float32, the inner sum left to right, every product and
+    every sum rounded on its own (the library is built without contraction). (row, col) float32 matrices."""
+    A, B = np.asarray(A, np.float32), np.asarray(B, np.float32)
+    C = np.zeros((4, 4), np.float32)
+    for c in range(4):
+        for r in range(4):
+            s = A[r, 0] * B[0, c]
+            s = s + A[r, 1] * B[1, c]
+            s = s + A[r, 2] * B[2, c]
+            s = s + A[r, 3] * B[3, c]
+            C[r, c] = s
+    return C
+
+
+def history_transform(hist_T, T_odometry, index):
+    """The transform computeResidualsAgainstPreviousImage(index) inverts (:901-909): I odomBuffer[(index - 4) % 5] ...
+    odomBuffer[(index - 1) % 5] T_odometry, each product as mul4_cm evaluates it -- bit for bit the float32 matrix the stage
+    hands to its inverse. hist_T: the five ring slots ((row, col) float32 matrices; slots the chain does not read may be None)."""
+    T = np.eye(4, dtype=np.float32)
+    for i in range(index - HISTORY + 1, index):
+        T = mul4_cm_f32(T, hist_T[i % HISTORY])
+    return mul4_cm_f32(T, T_odometry)
+
+
+def residual_sources(d_old, d_cur, tan_half_fovh):
+    """The sources of the stage's splat: the old depth where it and the CURRENT depth are not 0 (Src::load of sf_residuals.h;
+    reference :1232), and xxBuffer / yyBuffer (:922-926) in float32 as every implementation evaluates them:
+    (inv_f_i (u - disp_u)) z, inv_f_i = 2 tan / cols."""
+    rows, cols = np.shape(d_old)
+    inv_f_i = np.float32(2.0) * np.float32(tan_half_fovh) / np.float32(cols)
+    _, disp_u, disp_v = warp_geometry(rows, cols, tan_half_fovh)
+    z = np.where(np.asarray(d_cur, np.float32) != 0, np.asarray(d_old, np.float32), np.float32(0)).astype(np.float32)
+    xs = inv_f_i * (np.arange(cols, dtype=np.float32) - np.float32(disp_u))
+    ys = inv_f_i * (np.arange(rows, dtype=np.float32) - np.float32(disp_v))
+    return z, (xs[None, :] * z).astype(np.float32), (ys[:, None] * z).astype(np.float32)
+
+
+def _residual_terms(W, SD, SI, SE, CNT, dc, idf, k):
+    """From the sums of a cell: the term t, whether the cell counts as far as the warp decides (touched, warped depth not 0),
+    and e_t per summation path of the splat (see the counts above)."""
+    Wd = np.maximum(W, 1).astype(np.float64)
+    cell = dict(depth=SD / Wd, intensity=SI / Wd, e_depth=SE / Wd, abs_depth=np.abs(SD) / Wd, abs_intensity=np.abs(SI) / Wd, count=CNT)
+    rd, ri = np.abs(dc - cell["depth"]), np.abs(idf - cell["intensity"])
+    t = rd + k * ri
+    e = {}
+    for ordered in (False, True):
+        bd, bi = warp_bounds(cell, ordered)
+        e[ordered] = SECOND_ORDER * (bd + k * bi + U32 * (rd + 2 * k * ri) + U32 * t)
+    return t, (W > 0) & (cell["depth"] != 0.0), e, cell
+
+
+def residuals_reference(d_old, i_old, d_cur, i_cur, labels0, T, tan_half_fovh, k_photometric_res, segmentation_enabled):
+    """perClusterAverageResidual of computeResidualsAgainstPreviousImage: the images pushed five frames ago (d_old, i_old) warped
+    by T^-1 (T: history_transform) onto the current ones, t = |d_cur - d_w| + k |idiff - i_w| summed per level-0 label over the
+    target pixels that are touched, have a current depth, a warped depth and a label below 24; idiff = i_cur where the old depth
+    of that pixel is not 0, else 0 (:937, :1022); result sum t / (2 (c + 1)), NaN for c = 0. Without segmentation every pixel has
+    label 0 (clusterAllocation[0] keeps its constructor value).
+
+    The splat is warp_reference's (section A). A source whose centi-pixel truncation the float evaluation could put on either
+    side cannot be left out of a SUM: for every cell such sources reach, the term is evaluated under every combination of their
+    candidate positions (each source: the distinct weights it can give that cell; beyond MAX_COMBINATIONS the ranges of d_w
+    and i_w over the extreme weights -- a weighted mean is linear-fractional in each weight -- and interval arithmetic), giving
+    [t_lo, t_hi] and whether the cell counts under all or only some of them.
+
+    Returns a dict of arrays over the 24 labels: `value` (the sources at their exact positions), `c`, `sum_abs`; `c_min`, `c_max`,
+    `s_lo`, `s_hi`; `sum_e[path]`, `bound[path]`, `lo[path]`, `hi[path]` for path "integer" (the splat's and the stage's
+    fixed-point sums), "ordered+integer" (the ordered float splat of an image of at most 2048 pixels on one workgroup, the
+    stage's fixed-point sums) and "float" (the reference's order in both); the admissible interval of a correct build is
+        [s_lo / (2 (c_max + 1)) - bound, s_hi / (2 (c_min + 1)) + bound];
+    and `terms` / `counted` / `depth_w` / `intensity_w` / `idiff` (planes, exact positions), `labels`, `k`, and what the scene exercised: n_sources, n_ambiguous,
+    n_ambiguous_cells, n_capped_cells, n_idiff_zero, n_invalid_label, n_untouched."""
+    import itertools
+
+    d_old, i_old, d_cur, i_cur = (np.asarray(a, np.float32).astype(np.float64) for a in (d_old, i_old, d_cur, i_cur))
+    rows, cols = d_cur.shape
+    lab = np.asarray(labels0).astype(np.int64) if segmentation_enabled else np.zeros((rows, cols), np.int64)
+    k = float(np.float32(k_photometric_res))
+    z, xx, yy = residual_sources(d_old, d_cur, tan_half_fovh)
+    ref = warp_reference(z, i_old, xx, yy, T, tan_half_fovh)
+    idiff = np.where(d_old != 0.0, i_cur, 0.0)
+    eligible = (d_cur != 0.0) & (lab < N_LABELS)
+    sm = ref["sums"]
+    paths = (False, True)  # the splat's: integer, ordered float
+
+    # -- the cells no ambiguous source reaches
+    t, counts, e, _ = _residual_terms(sm["w"], sm["depth"], sm["intensity"], sm["e_depth"], sm["count"], d_cur, idiff, k)
+    sure = eligible & ref["checked"] & counts
+    binsum = lambda mask, w=None: np.bincount(lab[mask], weights=None if w is None else w[mask], minlength=N_LABELS)[:N_LABELS].astype(np.float64)
+    c_min = binsum(sure)
+    c_max = c_min.copy()
+    c_nom = c_min.copy()
+    s_lo = binsum(sure, t)
+    s_hi, s_nom = s_lo.copy(), s_lo.copy()
+    sum_e = {p: binsum(sure, e[p]) for p in paths}
+    terms = np.where(sure, t, np.nan)
+    counted = sure.copy()
+    Wd = np.maximum(sm["w"], 1).astype(np.float64)
+    depth_w, intensity_w = np.where(sure, sm["depth"] / Wd, np.nan), np.where(sure, sm["intensity"] / Wd, np.nan)
+
+    # -- the cells they reach
+    amb = ref["ambiguous"]
+    cols_lim, rows_lim = 100 * (cols - 1), 100 * (rows - 1)
+    cand, nominal, reach = [], [], {}
+    for s in range(amb["depth_w"].size):
+        cl, cells = [], set()
+        for a in range(int(amb["u_lo"][s]), int(amb["u_hi"][s]) + 1):
+            for b in range(int(amb["v_lo"][s]), int(amb["v_hi"][s]) + 1):
+                taps = {}
+                if 0 <= a < cols_lim and 0 <= b < rows_lim:
+                    tv, tu, w = _taps(np.array([a]), np.array([b]))
+                    taps = {(int(tv[q, 0]), int(tu[q, 0])): int(w[q, 0]) for q in range(4) if w[q, 0] > 0}
+                if (a, b) == (int(amb["u_exact"][s]), int(amb["v_exact"][s])):
+                    nominal.append(len(cl))
+                cl.append(taps)
+                cells |= set(taps)
+        cand.append(cl)
+        for cell in cells:
+            reach.setdefault(cell, []).append(s)
+    assert len(nominal) == len(cand)
+    assert all(not ref["checked"][cell] for cell in reach)
+    rec = []  # (cell number, is the exact placement, W, SD, SI, SE, CNT) of every enumerated combination
+    cells, capped = [], []
+    for cell, srcs in sorted(reach.items()):
+        if not eligible[cell]:
+            continue
+        base = [sm[q][cell] for q in ("w", "depth", "intensity", "e_depth", "count")]
+        opts = [sorted({cl.get(cell, 0) for cl in cand[s]}) for s in srcs]
+        nom = tuple(cand[s][nominal[s]].get(cell, 0) for s in srcs)
+        n_comb = int(np.prod([len(o) for o in opts], dtype=np.float64))
+        if n_comb > MAX_COMBINATIONS:
+            assert len(srcs) <= 16, "more than 16 ambiguous sources reach one cell: outside this reference's preconditions"
+            opts = [[o[0], o[-1]] for o in opts]
+            capped.append(len(cells))
+        combos = list(itertools.product(*opts))
+        if nom not in combos:
+            combos.append(nom)
+        for ws in combos:
+            r = list(base)
+            for s, w in zip(srcs, ws):
+                if w:
+                    r[0] += w
+                    r[1] += w * amb["depth_w"][s]
+                    r[2] += w * amb["intensity"][s]
+                    r[3] += w * amb["e_depth"][s]
+                    r[4] += 1
+            rec.append([len(cells), ws == nom] + r)
+        cells.append(cell)
+    n_cells = len(cells)
+    if n_cells:
+        R = np.array(rec, dtype=np.float64)
+        cid, is_nom = R[:, 0].astype(np.int64), R[:, 1] != 0
+        cv, cu = (np.array([c[q] for c in cells]) for q in (0, 1))
+        t, counts, e, cell_v = _residual_terms(R[:, 2], R[:, 3], R[:, 4], R[:, 5], R[:, 6], d_cur[cv, cu][cid], idiff[cv, cu][cid], k)
+        t_lo, t_hi = np.full(n_cells, np.inf), np.full(n_cells, -np.inf)
+        np.minimum.at(t_lo, cid[counts], t[counts])
+        np.maximum.at(t_hi, cid[counts], t[counts])
+        some = np.zeros(n_cells, bool)
+        some[cid[counts]] = True
+        always = np.ones(n_cells, bool)
+        always[cid[~counts]] = False
+        e_max = {p: np.zeros(n_cells) for p in paths}
+        for p in paths:
+            np.maximum.at(e_max[p], cid[counts], e[p][counts])
+        for q in capped:  # the extremes of d_w and i_w are among the enumerated corners; t between them by interval arithmetic
+            m = (cid == q) & counts
+            if m.any():
+                dc, idf = d_cur[cells[q]], idiff[cells[q]]
+                dl, dh, il, ih = cell_v["depth"][m].min(), cell_v["depth"][m].max(), cell_v["intensity"][m].min(), cell_v["intensity"][m].max()
+                t_lo[q] = max(0.0, dl - dc, dc - dh) + k * max(0.0, il - idf, idf - ih)
+                t_hi[q] = max(abs(dc - dl), abs(dc - dh)) + k * max(abs(idf - il), abs(idf - ih))
+        cl_lab = lab[cv, cu]
+        acc = lambda mask, w: np.bincount(cl_lab[mask], weights=w[mask], minlength=N_LABELS)[:N_LABELS]
+        one = np.ones(n_cells)
+        c_min += acc(always, one)
+        c_max += acc(some, one)
+        s_lo += acc(always, np.where(always, t_lo, 0.0))
+        s_hi += acc(some, np.where(some, t_hi, 0.0))
+        for p in paths:
+            sum_e[p] += acc(some, e_max[p])
+        nm = is_nom & counts
+        c_nom += np.bincount(cl_lab[cid[nm]], minlength=N_LABELS)[:N_LABELS]
+        s_nom += np.bincount(cl_lab[cid[nm]], weights=t[nm], minlength=N_LABELS)[:N_LABELS]
+        terms[cv[cid[nm]], cu[cid[nm]]] = t[nm]
+        counted[cv[cid[nm]], cu[cid[nm]]] = True
+        depth_w[cv[cid[nm]], cu[cid[nm]]] = cell_v["depth"][nm]
+        intensity_w[cv[cid[nm]], cu[cid[nm]]] = cell_v["intensity"][nm]
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        value = np.where(c_nom > 0, s_nom / (2.0 * (c_nom + 1.0)), np.nan)
+        top = s_hi / (2.0 * (c_min + 1.0))
+        # path -> (the splat's sums, the stage's sums)
+        parts = {"integer": (sum_e[False], c_max * FIX_RES_Q), "ordered+integer": (sum_e[True], c_max * FIX_RES_Q),
+                 "float": (sum_e[True], gamma(c_max) * s_hi)}
+        bound = {p: np.where(c_max > 0, (se + tail) / (2.0 * (c_min + 1.0)) + 2 * U32 * top, np.nan) for p, (se, tail) in parts.items()}
+        lo = {p: np.where(c_max > 0, s_lo / (2.0 * (c_max + 1.0)) - bound[p], np.nan) for p in bound}
+        hi = {p: np.where(c_max > 0, top + bound[p], np.nan) for p in bound}
+        sum_e = {p: se for p, (se, _) in parts.items()}
+    touched = (sm["w"] > 0) | ~ref["checked"]
+    return dict(value=value, c=c_nom.astype(np.int64), sum_abs=s_nom, c_min=c_min.astype(np.int64), c_max=c_max.astype(np.int64), s_lo=s_lo,
+                s_hi=s_hi, sum_e=sum_e, bound=bound, lo=lo, hi=hi, terms=terms, counted=counted, labels=lab,
+                depth_w=depth_w, intensity_w=intensity_w, idiff=idiff, k=k,
+                n_sources=ref["n_sources"], n_ambiguous=ref["n_ambiguous"], n_ambiguous_cells=n_cells, n_capped_cells=len(capped),
+                n_idiff_zero=int((counted & (d_old == 0.0)).sum()), n_invalid_label=int((lab >= N_LABELS).sum()),
+                n_untouched=int(((d_cur != 0.0) & ~touched).sum()))
+
+
+def check_residuals(ref, got, path):
+    """cluster_residuals() of a build against residuals_reference: the NaN pattern (a cluster whose count interval includes 0 may
+    be either) and the admissible interval. -> (failures, ratio): ratio is the largest |got - value| / bound -- above 1 only
+    where the ambiguous sources, not the roundings, decide -- over the clusters that have a value."""
+    got = np.asarray(got, np.float64)
+    fails, ratio = [], 0.0
+    for l in range(N_LABELS):
+        if ref["c_max"][l] == 0:
+            if not np.isnan(got[l]):
+                fails.append("label %d: %r for a cluster without a counted pixel" % (l, got[l]))
+        elif np.isnan(got[l]):
+            if ref["c_min"][l] > 0:
+                fails.append("label %d: NaN for a cluster of %d counted pixels" % (l, ref["c"][l]))
+        else:
+            if not ref["lo"][path][l] <= got[l] <= ref["hi"][path][l]:
+                fails.append("label %d (%d pixels): got %r outside [%r, %r], exact %r, |d| / bound = %.3g"
+                             % (l, ref["c"][l], got[l], ref["lo"][path][l], ref["hi"][path][l], ref["value"][l],
+                                abs(got[l] - ref["value"][l]) / ref["bound"][path][l]))
+            if ref["c"][l] > 0:
+                ratio = max(ratio, abs(got[l] - ref["value"][l]) / ref["bound"][path][l])
+    return fails, float(ratio)
+
+
+def segm_image_reference(labels0, b_segm, cluster_res, uncertain=None):
+    """buildSegmImage: per pixel clamp(b_segm[label], 0, 1), replaced by max(b, 1 - b) where double(residual) < 0.017; 1 for a
+    pixel without a cluster ("assume static"). All in float32, exact. cluster_res: the 24 residuals, or (lo, hi), the admissible
+    interval of each (NaN: an empty cluster, never below the threshold); a cluster whose interval straddles the threshold, or
+    that `uncertain` marks (it may or may not be empty), and whose value depends on the answer, is left out.
+    -> (image, checked pixels, number of clusters left out)"""
+    lab = np.asarray(labels0).astype(np.int64)
+    lo, hi = cluster_res if isinstance(cluster_res, tuple) else (cluster_res, cluster_res)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    b = np.minimum(np.maximum(np.asarray(b_segm, np.float32), np.float32(0)), np.float32(1))
+    flipped = np.maximum(b, np.float32(1) - b)
+    with np.errstate(invalid="ignore"):
+        below, some_below = hi < STATIC_RESIDUAL, lo < STATIC_RESIDUAL
+    open_ = (below != some_below) | (np.zeros(N_LABELS, bool) if uncertain is None else np.asarray(uncertain) & some_below)
+    open_ &= flipped != b
+    val = np.append(np.where(below, flipped, b), np.float32(1)).astype(np.float32)
+    idx = np.minimum(lab, N_LABELS)
+    return val[idx], ~np.append(open_, False)[idx], int(open_.sum())
