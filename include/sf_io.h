@@ -61,7 +61,8 @@ int sf_io_trajectory_line(double timestamp, const float pose[16], int rotate_by_
 /* Reconstruction::savePly (reference Reconstruction.cpp:358-455), the map half: binary little-endian PLY of the surfels
  * whose confidence exceeds conf_threshold -- x y z (float), red green blue (uchar, from the encoded colour), nx ny nz
  * (float, NEGATED as the reference does), radius (float). surfels: count x 12 floats in the global model's vertex
- * layout (sf_map_download). Returns the number of vertices written or a negative code. */
+ * layout (sf_map_download; sfw_extract of sf_map_window.h with min_confidence fetches a superset without the rest of the
+ * map -- its test is >=, this gate is the reference's strict >). Returns the number of vertices written or a negative code. */
 int sf_io_save_ply(const char *path, const float *surfels, int count, float conf_threshold);
 
 const char *sf_io_last_error(void);

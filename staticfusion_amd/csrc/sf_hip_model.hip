@@ -1,6 +1,6 @@
 // sf_hip_model.hip — libsf_hip.so, the map side of include/sf.h without OpenGL: the
 // frame-to-model prediction (sf_predict.h) and the surfel map -- index images, data association, fusion, cleaning (sf_fusion.h).
-#include "../../include/sf_migrate.h"  // sfm_map_rebind (struct sf_map is local to this file)
+#include "../../include/sf_migrate.h"  // sfm_map_rebind
 #include "sf_host.h"
 #include "sf_predict.h"
 #include "sf_fusion.h"
@@ -241,23 +241,7 @@ int sf_get_prediction(sf_handle *h, int stream, float *depth, float *intensity) 
     return SF_OK;
 }
 
-// ---- the surfel map (sf_fusion.h) ------------------------------------------------------------------
-struct sf_map {
-    sf_handle *h = nullptr;
-    int capacity = 0;
-    float *buf[2] = {nullptr, nullptr};  // the model lives in buf[0] between calls; buf[1] holds the merged model inside a fuse
-    int count = 0, tick = 1;
-    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    int stats[4] = {0, 0, 0, 0};
-    unsigned long long *keys = nullptr, *occ = nullptr;
-    unsigned *winner = nullptr, *meta = nullptr, *index_export = nullptr;
-    float *rec = nullptr;
-    unsigned char *flags = nullptr;
-    int *block_counts = nullptr;
-    bool have_index = false;
-    int epoch = 0;  // index images rendered since the key image was last filled with ones; tag = 255 - epoch
-    std::vector<void *> allocs;
-};
+// ---- the surfel map (sf_fusion.h; struct sf_map: sf_host.h) ------------------------------------------
 static int map_alloc_bytes(sf_map *m, void **p, size_t bytes) {
     void *q = nullptr;
     hipError_t e = hipMalloc(&q, bytes ? bytes : 1);

@@ -6,6 +6,8 @@
 //   sf_hip_model.hip   frame-to-model prediction and the surfel map without OpenGL (sf_predict.h, sf_fusion.h)
 //   sf_hip_migrate.hip single streams between handles, to and from host memory, back to constructor state (sf_migrate.h;
 //                      its interface is include/sf_migrate.h, symbols sfm_*)
+//   sf_hip_map_window.hip  bounded maps: count, cull, extract, page out, append (sf_map_window.h; its interface is
+//                      include/sf_map_window.h, symbols sfw_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,6 +109,24 @@ struct sf_handle {
     hipEvent_t mig_ev = nullptr;
     uint8_t *mig_stage = nullptr;
     size_t mig_stage_bytes = 0;
+};
+
+// the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
+struct sf_map {
+    sf_handle *h = nullptr;
+    int capacity = 0;
+    float *buf[2] = {nullptr, nullptr};  // the model lives in buf[0] between calls; buf[1] holds the merged model inside a fuse
+    int count = 0, tick = 1;
+    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int stats[4] = {0, 0, 0, 0};
+    unsigned long long *keys = nullptr, *occ = nullptr;
+    unsigned *winner = nullptr, *meta = nullptr, *index_export = nullptr;
+    float *rec = nullptr;
+    unsigned char *flags = nullptr;
+    int *block_counts = nullptr;
+    bool have_index = false;
+    int epoch = 0;  // index images rendered since the key image was last filled with ones; tag = 255 - epoch
+    std::vector<void *> allocs;
 };
 
 // Constructor state of a stream (reference FrontEnd.cpp:79-81,110,152-154), as the 32-bit word at byte offset `off` of its

@@ -7,7 +7,11 @@ the GPU and batched over the sequences:
 The decoded VGA frames of a synthetic walk are resident in HBM (every sequence sees the same walk; the work does not depend on
 that). Reports full-pipeline frames/s and the share of each stage (host wall time around synchronised calls).
 
-usage: python tools/full_pipeline_bench.py [--streams 256] [--frames 10] [--sphere]
+With --max-age N and / or --window-radius R every map is culled in one sfw_cull_maps before each fuse (include/sf_map_window.h:
+what the camera has not seen for N ticks, or what is farther than R metres from it, leaves the map), and the cull is a fifth stage
+of the report. Without either flag nothing of that runs and the output is what it was.
+
+usage: python tools/full_pipeline_bench.py [--streams 256] [--frames 10] [--sphere] [--max-age N] [--window-radius R]
 """
 import argparse
 import ctypes as C
@@ -28,6 +32,8 @@ def main():
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--sphere", action="store_true")
     ap.add_argument("--capacity", type=int, default=0)
+    ap.add_argument("--max-age", type=int, default=-1, help="cull surfels not seen for more than this many ticks before each fuse")
+    ap.add_argument("--window-radius", type=float, default=0.0, help="cull surfels farther than this from the camera before each fuse")
     a = ap.parse_args()
     api = sf.load()
     rows, cols, res = 240, 320, 2
@@ -71,7 +77,13 @@ def main():
     Tq = s.batch_results()[0]
     s.filter_depth()
     sf.SurfelMap.fuse_frames(s, streams, maps, list(Tq), 1.0, mp)
+    window = a.max_age >= 0 or a.window_radius > 0
+    if window:
+        from staticfusion_amd import map_window
     stages = dict(predict=0.0, input=0.0, solve=0.0, fuse=0.0)
+    if window:
+        stages["cull"] = 0.0
+    culled = 0
     timed = 0
     t_start = None
     for k in range(2, a.frames):
@@ -91,9 +103,17 @@ def main():
         s.process_frame(k)
         Tq = s.batch_results()[0]
         t3 = time.perf_counter()
+        tf = t3
+        if window:
+            before = sum(m.info()["count"] for m in maps)
+            tc = time.perf_counter()
+            fl = [map_window.Filter(max_age=a.max_age, centre=map_window.camera_centre(m), radius=a.window_radius) for m in maps]
+            culled += before - sum(map_window.cull(maps, fl))  # returns after the counts have been read back
+            tf = time.perf_counter()
+            stages["cull"] += tf - tc
         sf.SurfelMap.fuse_frames(s, streams, maps, list(Tq), 1.0, mp)
         t4 = time.perf_counter()
-        for name, dt in zip(("predict", "input", "solve", "fuse"), (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+        for name, dt in zip(("predict", "input", "solve", "fuse"), (t1 - t0, t2 - t1, t3 - t2, t4 - tf)):
             stages[name] += dt
         timed += 1
     total = time.perf_counter() - t_start
@@ -101,7 +121,9 @@ def main():
     err = pose_delta(info["pose"], gts[a.frames - 1])
     print("full pipeline, %d sequences x %d timed frames (%s): %.2f ms per step, %.0f frames/s; map %d surfels; pose error vs ground truth %.2e rad %.2e m"
           % (n, timed, "moving sphere" if a.sphere else "static", 1e3 * total / timed, n * timed / total, info["count"], err[0], err[1]))
-    for name in ("predict", "input", "solve", "fuse"):
+    if window:
+        print("  window: max age %d, radius %g: %d surfels culled in all" % (a.max_age, a.window_radius, culled))
+    for name in stages:
         print("  %-8s %8.2f ms per step  %5.1f %%   %7.1f us per sequence" % (name, 1e3 * stages[name] / timed, 100 * stages[name] / total, 1e6 * stages[name] / timed / n))
 
 
