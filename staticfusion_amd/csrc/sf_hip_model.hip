@@ -24,7 +24,7 @@ int sf_default_model_params(const sf_handle *h, sf_model_params *p) {
     return SF_OK;
 }
 // 4x4 inverse, double Gauss-Jordan with partial pivoting, rounded to float (the [C5] convention of the solver)
-static void invert_pose(const float pose[16], float out[16]) {
+void invert_pose(const float pose[16], float out[16]) {  // (shared: sf_host.h)
     double A[16], Ai[16];
     for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) {

@@ -8,6 +8,8 @@
 //                      its interface is include/sf_migrate.h, symbols sfm_*)
 //   sf_hip_map_window.hip  bounded maps: count, cull, extract, page out, append (sf_map_window.h; its interface is
 //                      include/sf_map_window.h, symbols sfw_*)
+//   sf_hip_view.hip    maps drawn from any view: depth, colour and index images (sf_view.h; its interface is
+//                      include/sf_view.h, symbols sfv_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -109,6 +111,14 @@ struct sf_handle {
     hipEvent_t mig_ev = nullptr;
     uint8_t *mig_stage = nullptr;
     size_t mig_stage_bytes = 0;
+    // free-view rendering (sf_hip_view.hip): one block for the key images, ray tables, large-sprite lists, argument tables and
+    // output staging of a call, grown when a call needs more (dev_grow: in h->allocs, freed with the handle); the host copy
+    // the tables are filled from; where the per-view list counters of the last call lie in the block
+    unsigned char *view_scratch = nullptr;
+    size_t view_bytes = 0;
+    std::vector<unsigned char> view_tab_host;
+    size_t view_counters_off = 0;
+    int view_last_n = 0;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -207,5 +217,6 @@ SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 //
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
 SF_INTERNAL int input_alloc(sf_handle *h);                                    // sf_hip_input.hip: buffers of the input stage, on first use
 SF_INTERNAL void orphan_maps(sf_handle *h);                                   // sf_hip_model.hip: sf_destroy releases the handle's maps
+SF_INTERNAL void invert_pose(const float pose[16], float out[16]);            // sf_hip_model.hip: t_inv of the prediction, the fusion and the views
 SF_INTERNAL void migrate_release(sf_handle *h);                               // sf_hip_migrate.hip: sf_destroy releases the pinned tables and events
 }

@@ -1,0 +1,297 @@
+// sf_view.h — device code of include/sf_view.h (host side: sf_hip_view.hip): a surfel buffer drawn from any pose, with any
+// pinhole intrinsics, at any size, into a depth, a colour and an index image. The geometry is ONE target of
+// IndexMap::combinedPredict exactly as sf_predict.h states it (splat.vert, combo_splat.frag): visibility is one 64-bit
+// atomicMin per fragment on (bits of gl_FragDepth) << 32 | surfel index, so the images do not depend on the execution
+// order, and every float expression below repeats the association of sf_predict.h (no contraction). That header defines
+// kernels, so it cannot be included by a second translation unit of the library: its camera transform, sprite extent and
+// fragment test are restated here on ViewArgs.
+//
+// Four launches serve a whole batch of views (table entry blockIdx.y, like PredictArgs / WindowArgs): clear, splat (a lane
+// per surfel), large sprites (a wave per listed surfel), resolve (a lane per pixel). A fifth, in front, builds the view-ray
+// table of every distinct (rows, cols, cx, cy, fx, fy) of the call.
+#pragma once
+#include "sf_device_common.h"
+
+struct ViewArgs {
+    const float *surfels;  // count x 12
+    int count;
+    float t_inv[16];       // column-major
+    float cx, cy, fx, fy, max_depth, min_confidence;
+    float tick, max_age;   // (float)tick of the map, (float)max_age
+    int use_age;           // max_age >= 0
+    int shade;             // SFV_SHADE_*
+    int rows, cols;
+    unsigned long long *keys;  // rows x cols, column-major
+    const vfloat4 *rays;       // per pixel, column-major: normalize((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1)
+    int *large_count;          // [1]: length of large_list
+    int *large_list;           // [count]: surfels whose clipped sprite has more than SFV_LARGE_PIXELS pixels
+    float *depth;              // rows x cols row-major, or null
+    uint8_t *rgb;              // rows x cols x 3 row-major, or null
+    int *index;                // rows x cols row-major, or null
+};
+struct ViewRayArgs {
+    vfloat4 *rays;
+    int rows, cols;
+    float cx, cy, fx, fy;
+};
+
+#define SFV_EMPTY 0xffffffffffffffffull
+#define SFV_SPLAT_NT 512
+// One target, so the 48 KB that hold the prediction's two tiles of 3072 pixels could hold one of 6144 here -- or the same
+// 3072 pixels in 24 KB at a higher occupancy. The kernel needs 45 VGPRs (8 waves per SIMD by registers): with 24 KB four
+// 512-thread workgroups are resident per CU (8 waves per SIMD), with 48 KB three (6, the prediction's occupancy). Both were
+// built and run alternately (tools/view_bench.py): the small tile is faster in every case, 9 % for
+// 256 QVGA views, 3.5 % for a 1280 x 960 orbit where more workgroups leave the LDS path.
+#ifndef SFV_SPLAT_TILE  // (an A/B build sets another: tools/build_variant.sh, tools/view_bench.py under SF_HIP_LIB)
+#define SFV_SPLAT_TILE 3072
+#endif
+// A surfel whose clipped sprite has more pixels than this is not walked by its lane: a whole wave draws it (sfv_large_kernel)
+#define SFV_LARGE_PIXELS 1024  // 32 x 32
+#define SFV_LARGE_NT 256
+#define SFV_LARGE_BLOCKS 64    // workgroups per view that walk its list (4 waves each)
+
+struct VV3 { float x, y, z; };
+__device__ __forceinline__ float vdot(VV3 a, VV3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ VV3 vadd(VV3 a, VV3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ VV3 vsub(VV3 a, VV3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ VV3 vmul(VV3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ VV3 vnormalize(VV3 a) {
+    const float n = sqrtf(vdot(a, a));
+    return {a.x / n, a.y / n, a.z / n};
+}
+__device__ __forceinline__ VV3 vcross(VV3 a, VV3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
+
+// camera-frame position, normal and radius of surfel s (splat.vert:55,68); false if culled: depth range, confidence
+// (!(s[3] < min_confidence) draws: a NaN confidence is drawn), age (test B of sfw_filter: a NaN s[7] is not drawn)
+__device__ __forceinline__ bool sfv_to_camera(const ViewArgs &a, int s, VV3 &h, VV3 &n, float &rad) {
+    const auto q = as_global(a.surfels) + (size_t)s * 12;
+    const float *T = a.t_inv;
+    const VV3 vp{q[0], q[1], q[2]};
+    const float conf = q[3], tlast = q[7];
+    h = VV3{T[0] * vp.x + T[4] * vp.y + T[8] * vp.z + T[12], T[1] * vp.x + T[5] * vp.y + T[9] * vp.z + T[13],
+            T[2] * vp.x + T[6] * vp.y + T[10] * vp.z + T[14]};
+    const VV3 nin{q[8], q[9], q[10]};
+    n = vnormalize(VV3{T[0] * nin.x + T[4] * nin.y + T[8] * nin.z, T[1] * nin.x + T[5] * nin.y + T[9] * nin.z,
+                       T[2] * nin.x + T[6] * nin.y + T[10] * nin.z});
+    rad = q[11];
+    if (h.z > a.max_depth || h.z < 0.4f || conf < a.min_confidence) return false;
+    if (a.use_age && !(a.tick - tlast <= a.max_age)) return false;
+    return true;
+}
+
+// combo_splat.frag:37-49,63 for the fragment at pixel (i, j); false = discard
+__device__ __forceinline__ bool sfv_fragment(const ViewArgs &a, VV3 h, VV3 n, float rad, int i, int j, float &z, float &depth) {
+    const vfloat4 lr = as_global(a.rays)[j + (size_t)i * a.rows];
+    const VV3 l{lr.x, lr.y, lr.z};
+    const VV3 corrected = vmul(l, vdot(h, n) / vdot(l, n));
+    const VV3 diff = vsub(corrected, h);
+    if (vdot(diff, diff) > rad * rad) return false;
+    z = corrected.z;
+    depth = (corrected.z / (2.f * a.max_depth)) + 0.5f;
+    return depth >= 0.f && depth < 1.f;
+}
+
+// what surfel s draws: camera-frame geometry and the clipped pixel rectangle [i0, i1] x [j0, j1] of its sprite
+// (splat.vert:57-85 as sf_predict_splat_kernel states it); false: nothing
+__device__ __forceinline__ bool sfv_sprite(const ViewArgs &a, int s, VV3 &h, VV3 &n, float &rad, int &i0, int &i1, int &j0, int &j1) {
+    if (!sfv_to_camera(a, s, h, n, rad)) return false;
+    const float fcols = float(a.cols), frows = float(a.rows);
+    const float ndc_x = ((((a.fx * h.x) / h.z) + a.cx) - (fcols * 0.5f)) / (fcols * 0.5f);
+    const float ndc_y = ((((a.fy * h.y) / h.z) + a.cy) - (frows * 0.5f)) / (frows * 0.5f);
+    if (!(ndc_x >= -1.f && ndc_x <= 1.f && ndc_y >= -1.f && ndc_y <= 1.f)) return false;  // centre outside the image: not drawn
+    const float xw = (ndc_x + 1.f) * (fcols * 0.5f), yw = (ndc_y + 1.f) * (frows * 0.5f);
+    const VV3 x1 = vmul(vmul(vnormalize(VV3{n.y - n.z, -n.x, n.x}), rad), 1.41421356f);
+    const VV3 y1 = vcross(n, x1);
+    const VV3 c1 = vadd(h, x1), c2 = vadd(h, y1), c3 = vsub(h, y1), c4 = vsub(h, x1);
+    const float p1x = ((a.fx * c1.x) / c1.z) + a.cx, p1y = ((a.fy * c1.y) / c1.z) + a.cy;
+    const float p2x = ((a.fx * c2.x) / c2.z) + a.cx, p2y = ((a.fy * c2.y) / c2.z) + a.cy;
+    const float p3x = ((a.fx * c3.x) / c3.z) + a.cx, p3y = ((a.fy * c3.y) / c3.z) + a.cy;
+    const float p4x = ((a.fx * c4.x) / c4.z) + a.cx, p4y = ((a.fy * c4.y) / c4.z) + a.cy;
+    const float xlo = fminf(p1x, fminf(p2x, fminf(p3x, p4x))), xhi = fmaxf(p1x, fmaxf(p2x, fmaxf(p3x, p4x)));
+    const float ylo = fminf(p1y, fminf(p2y, fminf(p3y, p4y))), yhi = fmaxf(p1y, fmaxf(p2y, fmaxf(p3y, p4y)));
+    const float xDiff = fabsf(xhi - xlo), yDiff = fabsf(yhi - ylo);
+    const float size = fmaxf(0.f, fmaxf(xDiff, yDiff));
+    if (!(size > 0.f)) return false;
+    const float half = size * 0.5f;
+    i0 = max(0, (int)ceilf(xw - half - 0.5f)); i1 = min(a.cols - 1, (int)floorf(xw + half - 0.5f));
+    j0 = max(0, (int)ceilf(yw - half - 0.5f)); j1 = min(a.rows - 1, (int)floorf(yw + half - 0.5f));
+    // a fragment survives only inside the disc, which lies inside the diamond of the four projected corners: pixels outside
+    // their bounding rectangle (+ 1 pixel against rounding at the rim) would be discarded anyway (sf_predict.h)
+    i0 = max(i0, (int)floorf(xlo - 1.5f)); i1 = min(i1, (int)ceilf(xhi + 0.5f));
+    j0 = max(j0, (int)floorf(ylo - 1.5f)); j1 = min(j1, (int)ceilf(yhi + 0.5f));
+    return i0 <= i1 && j0 <= j1;
+}
+
+__global__ __launch_bounds__(256) void sfv_rays_kernel(const ViewRayArgs *tab) {
+    const ViewRayArgs &a = tab[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;  // j + i * rows
+    if (idx >= a.rows * a.cols) return;
+    const int i = idx / a.rows, j = idx - i * a.rows;
+    const float fx_ = float(i) + 0.5f, fy_ = float(j) + 0.5f;  // gl_FragCoord
+    const VV3 l = vnormalize(VV3{(fx_ - a.cx) / a.fx, (fy_ - a.cy) / a.fy, 1.0f});
+    a.rays[idx] = vfloat4{l.x, l.y, l.z, 0.f};
+}
+
+__global__ __launch_bounds__(256) void sfv_clear_kernel(const ViewArgs *tab) {
+    const ViewArgs &a = tab[blockIdx.y];
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o < a.rows * a.cols) a.keys[o] = SFV_EMPTY;
+    if (o == 0) *a.large_count = 0;
+}
+
+// One lane per surfel, the plan of sf_predict_splat_kernel for one target: the workgroup resolves its fragments in an LDS
+// tile when the bounding box of its sprites fits and sends the tile's winners to the key image; otherwise one global
+// atomicMin per fragment. A sprite of more than SFV_LARGE_PIXELS pixels takes no part in either: it is listed.
+__global__ __launch_bounds__(SFV_SPLAT_NT) void sfv_splat_kernel(const ViewArgs *tab) {
+    __shared__ unsigned long long tile[SFV_SPLAT_TILE];
+    __shared__ int bb[4];
+    const ViewArgs &a = tab[blockIdx.y];
+    if ((int)blockIdx.x * SFV_SPLAT_NT >= a.count) return;  // a workgroup of a larger map of the batch
+    const int tid = threadIdx.x;
+    const int s = blockIdx.x * SFV_SPLAT_NT + tid;
+    VV3 h{0.f, 0.f, 1.f}, n{0.f, 0.f, 1.f};
+    float rad = 0.f;
+    int i0 = 0, i1 = -1, j0 = 0, j1 = -1;
+    bool valid = s < a.count && sfv_sprite(a, s, h, n, rad, i0, i1, j0, j1);
+    if (valid && (i1 - i0 + 1) * (j1 - j0 + 1) > SFV_LARGE_PIXELS) {
+        const int slot = __hip_atomic_fetch_add(as_global(a.large_count), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (slot < a.count) a.large_list[slot] = s;  // (always: a surfel is listed once)
+        valid = false;
+    }
+    if (tid == 0) {
+        bb[0] = bb[1] = 0x7fffffff;
+        bb[2] = bb[3] = -1;
+    }
+    __syncthreads();
+    if (valid) {
+        atomicMin(&bb[0], i0);
+        atomicMin(&bb[1], j0);
+        atomicMax(&bb[2], i1);
+        atomicMax(&bb[3], j1);
+    }
+    __syncthreads();
+    const int bi0 = bb[0], bj0 = bb[1], bw = bb[2] - bi0 + 1, bh = bb[3] - bj0 + 1;
+    if (bw <= 0 || bh <= 0) return;  // nothing to draw (uniform: read from LDS after the barrier)
+    const bool tiled = (long long)bw * bh <= SFV_SPLAT_TILE;
+    const bool wide = bw > bh;  // tile layout along the longer side of the box (sf_predict.h)
+    if (tiled) {
+        for (int q = tid; q < bw * bh; q += SFV_SPLAT_NT) tile[q] = SFV_EMPTY;
+        __syncthreads();
+    }
+    if (valid)
+        for (int i = i0; i <= i1; i++)
+            for (int j = j0; j <= j1; j++) {
+                float z, depth;
+                if (!sfv_fragment(a, h, n, rad, i, j, z, depth)) continue;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)s;
+                if (tiled) {
+                    const int t = wide ? (j - bj0) * bw + (i - bi0) : (i - bi0) * bh + (j - bj0);
+                    atomicMin(&tile[t], key);
+                } else {
+                    __hip_atomic_fetch_min(as_global(a.keys) + (j + (size_t)i * a.rows), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+    if (!tiled) return;
+    __syncthreads();
+    for (int q = tid; q < bw * bh; q += SFV_SPLAT_NT) {
+        const int i = bi0 + (wide ? q % bw : q / bh), j = bj0 + (wide ? q / bw : q % bh);
+        const unsigned long long k = tile[q];
+        if (k != SFV_EMPTY) __hip_atomic_fetch_min(as_global(a.keys) + (j + (size_t)i * a.rows), k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The listed sprites, one wave each: the 64 lanes walk the sprite's pixels in the key image's own (column-major) order, so a
+// wave's atomics fall on neighbouring words. A view from 0.4 m at four times QVGA has sprites of 10^5 pixels; one lane
+// walking one would hold up its whole workgroup. min is commutative and associative: whichever kernel draws a fragment, the
+// key image is the same.
+__global__ __launch_bounds__(SFV_LARGE_NT) void sfv_large_kernel(const ViewArgs *tab) {
+    const ViewArgs &a = tab[blockIdx.y];
+    const int n_listed = min(*a.large_count, a.count);
+    const int lane = threadIdx.x & 63;
+    const int waves = (int)gridDim.x * (SFV_LARGE_NT / 64);
+    for (int e = (int)blockIdx.x * (SFV_LARGE_NT / 64) + (int)(threadIdx.x >> 6); e < n_listed; e += waves) {
+        const int s = __builtin_amdgcn_readfirstlane(a.large_list[e]);
+        if (s < 0 || s >= a.count) continue;
+        VV3 h, n;
+        float rad;
+        int i0, i1, j0, j1;
+        if (!sfv_sprite(a, s, h, n, rad, i0, i1, j0, j1)) continue;  // (it was drawn when it was listed)
+        const int hgt = j1 - j0 + 1, total = (i1 - i0 + 1) * hgt;
+        const int di = 64 / hgt, dj = 64 - di * hgt;  // a step of 64 pixels in (column, row)
+        int i = i0 + lane / hgt, j = j0 + lane % hgt;
+        for (int q = lane; q < total; q += 64) {
+            float z, depth;
+            if (sfv_fragment(a, h, n, rad, i, j, z, depth)) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)s;
+                __hip_atomic_fetch_min(as_global(a.keys) + (j + (size_t)i * a.rows), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            i += di;
+            j += dj;
+            if (j > j1) {
+                j -= hgt;
+                i++;
+            }
+        }
+    }
+}
+
+// One lane per pixel: the winning fragment is evaluated again and depth / colour / index are written. A workgroup owns a
+// 32 x 32 tile. Phase 1 runs lanes along y, the direction of the column-major key image and ray table; the three results
+// cross an LDS tile and phase 2 stores them with lanes along x, the direction of the row-major outputs.
+#define SFV_T 32
+__global__ __launch_bounds__(256) void sfv_resolve_kernel(const ViewArgs *tab) {
+    __shared__ float t_z[SFV_T][SFV_T + 1];
+    __shared__ unsigned t_c[SFV_T][SFV_T + 1];
+    __shared__ int t_s[SFV_T][SFV_T + 1];
+    const ViewArgs &a = tab[blockIdx.y];
+    const int tiles_x = (a.cols + SFV_T - 1) / SFV_T, tiles_y = (a.rows + SFV_T - 1) / SFV_T;
+    if ((int)blockIdx.x >= tiles_x * tiles_y) return;  // a workgroup of a larger view of the batch
+    const int ty = (int)blockIdx.x % tiles_y, tx = (int)blockIdx.x / tiles_y;
+    const int x0 = tx * SFV_T, y0 = ty * SFV_T;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int yl = threadIdx.x & 31, xl = (threadIdx.x >> 5) + 8 * k;
+        const int x = x0 + xl, y = y0 + yl;
+        if (x >= a.cols || y >= a.rows) continue;
+        const unsigned long long key = as_global(a.keys)[y + (size_t)x * a.rows];
+        float z = 0.f;
+        unsigned c = 0u;
+        int s = -1;
+        if (key != SFV_EMPTY) {
+            s = (int)(unsigned)(key & 0xffffffffull);
+            VV3 h, n;
+            float rad, depth;
+            sfv_to_camera(a, s, h, n, rad);
+            sfv_fragment(a, h, n, rad, x, y, z, depth);
+            if (a.shade == 1) {  // SFV_SHADE_NORMAL
+                const float v[3] = {n.x, n.y, n.z};
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    const unsigned b = (unsigned)(uint8_t)(int)rintf(fminf(fmaxf(0.5f * v[q] + 0.5f, 0.f), 1.f) * 255.f);
+                    c |= b << (16 - 8 * q);
+                }
+            } else {
+                c = (unsigned)(int)as_global(a.surfels)[(size_t)s * 12 + 4] & 0xffffffu;  // color.glsl decodeColor
+            }
+        }
+        t_z[yl][xl] = z;
+        t_c[yl][xl] = c;
+        t_s[yl][xl] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int xl = threadIdx.x & 31, yl = (threadIdx.x >> 5) + 8 * k;
+        const int x = x0 + xl, y = y0 + yl;
+        if (x >= a.cols || y >= a.rows) continue;
+        const size_t o = (size_t)y * a.cols + x;
+        if (a.depth) a.depth[o] = t_z[yl][xl];
+        if (a.index) a.index[o] = t_s[yl][xl];
+        if (a.rgb) {
+            const unsigned c = t_c[yl][xl];
+            a.rgb[o * 3] = (uint8_t)(c >> 16);
+            a.rgb[o * 3 + 1] = (uint8_t)(c >> 8);
+            a.rgb[o * 3 + 2] = (uint8_t)c;
+        }
+    }
+}
