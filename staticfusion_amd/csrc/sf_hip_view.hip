@@ -25,73 +25,54 @@ static int check_view(const sfv_view *v) {
     return SF_OK;
 }
 
-struct ViewJob {
-    const float *d_surfels;  // device; null with upload != null: the scratch copy
-    int count, tick;
-};
-struct ViewOut {
-    void *depth, *rgb, *index;  // host or device pointers, any of them null
-};
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// n checked views: layout of the scratch block, tables, the five launches, and for host outputs the copies
-static int render(sf_handle *h, int n, const ViewJob *jobs, const sfv_view *views, const ViewOut *outs, bool device_out, const float *upload,
-                  int upload_count) {
-    HIP_TRY(hipSetDevice(h->device));
-    // ---- distinct ray tables
-    std::vector<int> ray_of((size_t)n);
-    std::vector<int> ray_first;  // view that introduced table r
-    for (int q = 0; q < n; q++) {
+// ---- the drawing stage (declared in sf_host.h: sf_hip_score.hip draws into a block of its own with it)
+void sfv_plan(ViewPlan &p, int n, const ViewJob *jobs, const sfv_view *views, int upload_count) {
+    p.n = n;
+    p.ray_of.assign((size_t)n, 0);
+    p.ray_first.clear();
+    for (int q = 0; q < n; q++) {  // distinct ray tables
         const sfv_view &v = views[q];
         int r = 0;
-        for (; r < (int)ray_first.size(); r++) {
-            const sfv_view &w = views[ray_first[(size_t)r]];
+        for (; r < (int)p.ray_first.size(); r++) {
+            const sfv_view &w = views[p.ray_first[(size_t)r]];
             if (w.rows == v.rows && w.cols == v.cols && w.cx == v.cx && w.cy == v.cy && w.fx == v.fx && w.fy == v.fy) break;
         }
-        if (r == (int)ray_first.size()) ray_first.push_back(q);
-        ray_of[(size_t)q] = r;
+        if (r == (int)p.ray_first.size()) p.ray_first.push_back(q);
+        p.ray_of[(size_t)q] = r;
     }
-    // ---- layout
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align256(off + bytes);
-        return o;
-    };
-    const size_t o_tab = take((size_t)n * sizeof(ViewArgs));
-    const size_t o_rtab = take(ray_first.size() * sizeof(ViewRayArgs));
-    const size_t o_counters = take((size_t)n * sizeof(int));
-    const size_t o_upload = take((size_t)upload_count * 12 * sizeof(float));
-    std::vector<size_t> o_rays(ray_first.size()), o_keys((size_t)n), o_list((size_t)n), o_depth((size_t)n), o_rgb((size_t)n), o_index((size_t)n);
-    for (size_t r = 0; r < ray_first.size(); r++) o_rays[r] = take((size_t)views[ray_first[r]].rows * views[ray_first[r]].cols * sizeof(vfloat4));
+    p.off = 0;
+    p.o_tab = p.take((size_t)n * sizeof(ViewArgs));
+    p.o_rtab = p.take(p.ray_first.size() * sizeof(ViewRayArgs));
+    p.o_counters = p.take((size_t)n * sizeof(int));
+    p.o_upload = p.take((size_t)upload_count * 12 * sizeof(float));
+    p.o_rays.resize(p.ray_first.size());
+    p.o_keys.resize((size_t)n);
+    p.o_list.resize((size_t)n);
+    for (size_t r = 0; r < p.ray_first.size(); r++)
+        p.o_rays[r] = p.take((size_t)views[p.ray_first[r]].rows * views[p.ray_first[r]].cols * sizeof(vfloat4));
     for (int q = 0; q < n; q++) {
-        const size_t px = (size_t)views[q].rows * views[q].cols;
-        o_keys[(size_t)q] = take(px * 8);
-        o_list[(size_t)q] = take((size_t)jobs[q].count * sizeof(int));
-        if (!device_out) {
-            if (outs[q].depth) o_depth[(size_t)q] = take(px * 4);
-            if (outs[q].rgb) o_rgb[(size_t)q] = take(px * 3);
-            if (outs[q].index) o_index[(size_t)q] = take(px * 4);
-        }
+        p.o_keys[(size_t)q] = p.take((size_t)views[q].rows * views[q].cols * 8);
+        p.o_list[(size_t)q] = p.take((size_t)jobs[q].count * sizeof(int));
     }
-    if (int e = dev_grow(h, &h->view_scratch, &h->view_bytes, off)) return e;
-    unsigned char *base = h->view_scratch;
-    // ---- tables
-    h->view_tab_host.resize(o_counters);
-    ViewArgs *tab = (ViewArgs *)(h->view_tab_host.data() + o_tab);
-    ViewRayArgs *rtab = (ViewRayArgs *)(h->view_tab_host.data() + o_rtab);
-    int max_count = 0, max_tiles = 0;
+}
+
+int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const sfv_view *views, const ViewOut *outs, unsigned char *base,
+                  std::vector<unsigned char> &tab_host, const float *upload, int upload_count) {
+    const int n = p.n;
+    tab_host.resize(p.o_counters);
+    ViewArgs *tab = (ViewArgs *)(tab_host.data() + p.o_tab);
+    ViewRayArgs *rtab = (ViewRayArgs *)(tab_host.data() + p.o_rtab);
+    int max_count = 0;
     size_t max_px = 0, max_ray_px = 0;
-    for (size_t r = 0; r < ray_first.size(); r++) {
-        const sfv_view &v = views[ray_first[r]];
-        rtab[r] = ViewRayArgs{(vfloat4 *)(base + o_rays[r]), v.rows, v.cols, v.cx, v.cy, v.fx, v.fy};
+    for (size_t r = 0; r < p.ray_first.size(); r++) {
+        const sfv_view &v = views[p.ray_first[r]];
+        rtab[r] = ViewRayArgs{(vfloat4 *)(base + p.o_rays[r]), v.rows, v.cols, v.cx, v.cy, v.fx, v.fy};
         max_ray_px = std::max(max_ray_px, (size_t)v.rows * v.cols);
     }
     for (int q = 0; q < n; q++) {
         const sfv_view &v = views[q];
         ViewArgs &a = tab[q];
-        a.surfels = jobs[q].d_surfels ? jobs[q].d_surfels : (const float *)(base + o_upload);
+        a.surfels = jobs[q].d_surfels ? jobs[q].d_surfels : (const float *)(base + p.o_upload);
         a.count = jobs[q].count;
         invert_pose(v.pose, a.t_inv);  // the prediction's t_inv = pose.inverse()
         a.cx = v.cx; a.cy = v.cy; a.fx = v.fx; a.fy = v.fy;
@@ -102,29 +83,22 @@ static int render(sf_handle *h, int n, const ViewJob *jobs, const sfv_view *view
         a.use_age = v.max_age >= 0;
         a.shade = v.shade;
         a.rows = v.rows; a.cols = v.cols;
-        a.keys = (unsigned long long *)(base + o_keys[(size_t)q]);
-        a.rays = (const vfloat4 *)(base + o_rays[(size_t)ray_of[(size_t)q]]);
-        a.large_count = (int *)(base + o_counters) + q;
-        a.large_list = (int *)(base + o_list[(size_t)q]);
-        if (device_out) {
-            a.depth = (float *)outs[q].depth;
-            a.rgb = (uint8_t *)outs[q].rgb;
-            a.index = (int *)outs[q].index;
-        } else {
-            a.depth = outs[q].depth ? (float *)(base + o_depth[(size_t)q]) : nullptr;
-            a.rgb = outs[q].rgb ? (uint8_t *)(base + o_rgb[(size_t)q]) : nullptr;
-            a.index = outs[q].index ? (int *)(base + o_index[(size_t)q]) : nullptr;
-        }
+        a.keys = (unsigned long long *)(base + p.o_keys[(size_t)q]);
+        a.rays = (const vfloat4 *)(base + p.o_rays[(size_t)p.ray_of[(size_t)q]]);
+        a.large_count = (int *)(base + p.o_counters) + q;
+        a.large_list = (int *)(base + p.o_list[(size_t)q]);
+        a.depth = outs ? (float *)outs[q].depth : nullptr;
+        a.rgb = outs ? (uint8_t *)outs[q].rgb : nullptr;
+        a.index = outs ? (int *)outs[q].index : nullptr;
         max_count = std::max(max_count, a.count);
         max_px = std::max(max_px, (size_t)v.rows * v.cols);
-        max_tiles = std::max(max_tiles, ((v.rows + SFV_T - 1) / SFV_T) * ((v.cols + SFV_T - 1) / SFV_T));
     }
-    HIP_TRY(hipMemcpyAsync(base, h->view_tab_host.data(), o_counters, hipMemcpyHostToDevice, h->stream));
-    if (upload_count) HIP_TRY(hipMemcpyAsync(base + o_upload, upload, (size_t)upload_count * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    const ViewArgs *d_tab = (const ViewArgs *)(base + o_tab);
+    HIP_TRY(hipMemcpyAsync(base, tab_host.data(), p.o_counters, hipMemcpyHostToDevice, h->stream));
+    if (upload_count) HIP_TRY(hipMemcpyAsync(base + p.o_upload, upload, (size_t)upload_count * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const ViewArgs *d_tab = (const ViewArgs *)(base + p.o_tab);
     const unsigned nv = (unsigned)n;
-    hipLaunchKernelGGL(sfv_rays_kernel, dim3((unsigned)((max_ray_px + 255) / 256), (unsigned)ray_first.size()), dim3(256), 0, h->stream,
-                       (const ViewRayArgs *)(base + o_rtab));
+    hipLaunchKernelGGL(sfv_rays_kernel, dim3((unsigned)((max_ray_px + 255) / 256), (unsigned)p.ray_first.size()), dim3(256), 0, h->stream,
+                       (const ViewRayArgs *)(base + p.o_rtab));
     hipLaunchKernelGGL(sfv_clear_kernel, dim3((unsigned)((max_px + 255) / 256), nv), dim3(256), 0, h->stream, d_tab);
     if (max_count) {
         hipLaunchKernelGGL(sfv_splat_kernel, dim3((unsigned)((max_count + SFV_SPLAT_NT - 1) / SFV_SPLAT_NT), nv), dim3(SFV_SPLAT_NT), 0, h->stream, d_tab);
@@ -132,9 +106,40 @@ static int render(sf_handle *h, int n, const ViewJob *jobs, const sfv_view *view
         hipLaunchKernelGGL(sfv_large_kernel, dim3((unsigned)std::min(SFV_LARGE_BLOCKS, (max_count + per_block - 1) / per_block), nv), dim3(SFV_LARGE_NT), 0,
                            h->stream, d_tab);
     }
-    hipLaunchKernelGGL(sfv_resolve_kernel, dim3((unsigned)max_tiles, nv), dim3(256), 0, h->stream, d_tab);
     HIP_TRY(hipGetLastError());
-    h->view_counters_off = o_counters;
+    return SF_OK;
+}
+
+// n checked views: the drawing stage into the handle's view scratch, then resolve and -- for host outputs -- the copies
+static int render(sf_handle *h, int n, const ViewJob *jobs, const sfv_view *views, const ViewOut *outs, bool device_out, const float *upload,
+                  int upload_count) {
+    HIP_TRY(hipSetDevice(h->device));
+    ViewPlan p;
+    sfv_plan(p, n, jobs, views, upload_count);
+    std::vector<size_t> o_depth((size_t)n), o_rgb((size_t)n), o_index((size_t)n);
+    int max_tiles = 0;
+    for (int q = 0; q < n; q++) {
+        const size_t px = (size_t)views[q].rows * views[q].cols;
+        if (!device_out) {
+            if (outs[q].depth) o_depth[(size_t)q] = p.take(px * 4);
+            if (outs[q].rgb) o_rgb[(size_t)q] = p.take(px * 3);
+            if (outs[q].index) o_index[(size_t)q] = p.take(px * 4);
+        }
+        max_tiles = std::max(max_tiles, ((views[q].rows + SFV_T - 1) / SFV_T) * ((views[q].cols + SFV_T - 1) / SFV_T));
+    }
+    if (int e = dev_grow(h, &h->view_scratch, &h->view_bytes, p.off)) return e;
+    unsigned char *base = h->view_scratch;
+    std::vector<ViewOut> staged;
+    if (!device_out) {
+        staged.resize((size_t)n);
+        for (int q = 0; q < n; q++)
+            staged[(size_t)q] = ViewOut{outs[q].depth ? base + o_depth[(size_t)q] : nullptr, outs[q].rgb ? base + o_rgb[(size_t)q] : nullptr,
+                                        outs[q].index ? base + o_index[(size_t)q] : nullptr};
+    }
+    if (int e = sfv_draw_keys(h, p, jobs, views, device_out ? outs : staged.data(), base, h->view_tab_host, upload, upload_count)) return e;
+    hipLaunchKernelGGL(sfv_resolve_kernel, dim3((unsigned)max_tiles, (unsigned)n), dim3(256), 0, h->stream, (const ViewArgs *)(base + p.o_tab));
+    HIP_TRY(hipGetLastError());
+    h->view_counters_off = p.o_counters;
     h->view_last_n = n;
     if (device_out) return SF_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));  // the images are in the block, and an uploaded host buffer is free again

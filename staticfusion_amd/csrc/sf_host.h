@@ -10,6 +10,8 @@
 //                      include/sf_map_window.h, symbols sfw_*)
 //   sf_hip_view.hip    maps drawn from any view: depth, colour and index images (sf_view.h; its interface is
 //                      include/sf_view.h, symbols sfv_*)
+//   sf_hip_score.hip   poses scored against maps: frame-to-map agreement counts (sf_score.h; its interface is
+//                      include/sf_score.h, symbols sfs_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -119,6 +121,11 @@ struct sf_handle {
     std::vector<unsigned char> view_tab_host;
     size_t view_counters_off = 0;
     int view_last_n = 0;
+    // pose scoring (sf_hip_score.hip): a block of its own with the same drawing layout (ViewPlan) followed by the score
+    // table, the result records and -- for the host-pointer calls -- the uploaded frames and the class images
+    unsigned char *score_scratch = nullptr;
+    size_t score_bytes = 0;
+    std::vector<unsigned char> score_tab_host, score_args_host;  // the host copies of the view table and the score table
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -212,6 +219,34 @@ SF_INTERNAL int launch(sf_handle *h, int mask, int im_count, int n_frames = 1, c
 SF_INTERNAL int solve_mask(const sf_handle *h, int create_image_pyr);                                            // sf_hip.hip
 SF_INTERNAL int pass_window_px(int resident_workgroups);                                                          // sf_hip.hip
 SF_INTERNAL bool use_five_per_cu(const sf_handle *h);                                                           // sf_hip.hip
+// The drawing stage of a batch of views, shared by the render calls and the score calls (sf_hip_view.hip). sfv_plan lays the
+// tables, ray tables, key images and large-sprite lists of n checked views out from offset 0 of a block; the caller takes
+// what else it needs behind them (ViewPlan::take), grows its block to ViewPlan::off bytes and hands it to sfv_draw_keys,
+// which fills and uploads the tables and launches rays, clear, splat and large sprites on the handle's stream. Afterwards
+// the key image of view q is complete at base + o_keys[q] and its ViewArgs at d_tab[q].
+struct ViewJob {
+    const float *d_surfels;  // device; null with upload != null: the uploaded copy in the block
+    int count, tick;
+};
+struct ViewOut {
+    void *depth, *rgb, *index;  // device pointers of the resolve kernel's outputs, any of them null
+};
+struct ViewPlan {
+    int n = 0;
+    std::vector<int> ray_of;     // per view: its ray table
+    std::vector<int> ray_first;  // per ray table: the view that introduced it
+    size_t off = 0;              // bytes laid out so far
+    size_t o_tab = 0, o_rtab = 0, o_counters = 0, o_upload = 0;
+    std::vector<size_t> o_rays, o_keys, o_list;
+    size_t take(size_t bytes) {  // 256-byte aligned
+        const size_t o = off;
+        off = (off + bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+SF_INTERNAL void sfv_plan(ViewPlan &p, int n, const ViewJob *jobs, const struct sfv_view *views, int upload_count);
+SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const struct sfv_view *views, const ViewOut *outs,
+                              unsigned char *base, std::vector<unsigned char> &tab_host, const float *upload, int upload_count);
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
