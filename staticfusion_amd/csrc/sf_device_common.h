@@ -235,6 +235,38 @@ __device__ __forceinline__ float wave_max_f32(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(b, 63));
 }
 
+// Exclusive scan of block_counts[0 .. n_blocks) in place by ONE 1024-thread workgroup, 1024 counts per trip; thread 0 gets the
+// total. The scan stage of the ordered compactions (sf_fusion.h: clean; sf_map_window.h: partition).
+__device__ __forceinline__ int block_counts_scan(int *block_counts, int n_blocks) {
+    __shared__ int wsum[16];
+    __shared__ int base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) base = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < n_blocks; c0 += 1024) {
+        const int idx = c0 + tid;
+        const int v = idx < n_blocks ? block_counts[idx] : 0;
+        int incl = v;  // inclusive scan within the wave (DPP-free, shuffle based: not a hot loop)
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; w++) off += wsum[w];
+        if (idx < n_blocks) block_counts[idx] = off + incl - v;
+        __syncthreads();
+        if (tid == 0) {
+            int t = 0;
+            for (int w = 0; w < 16; w++) t += wsum[w];
+            base += t;
+        }
+        __syncthreads();
+    }
+    return base;
+}
+
 // x86 cvttss2si semantics of the reference's int(float) (reference FrontEnd.cpp:819-820): NaN and
 // out-of-range -> INT_MIN.  (v_cvt_i32_f32 would saturate and turn NaN into 0, which the
 // reference's `uwarp >= 0` test would then ACCEPT.)

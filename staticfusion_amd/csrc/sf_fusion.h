@@ -23,7 +23,7 @@
 // to the CPU oracle (oracle/sf_oracle_fusion.cpp states the choices made where GL leaves room).
 #pragma once
 #include "../../include/sf_detmath.h"
-#include "sf_predict.h"
+#include "sf_surfel_geom.h"  // PV3 and its helpers
 
 #define SF_FUSE_NONE 0xffffffffu
 
@@ -465,35 +465,9 @@ __global__ __launch_bounds__(SF_CLEAN_BLOCK) void sf_clean_flag_kernel(const Fus
 }
 // exclusive scan of the block counts in place (one workgroup), totals into result[0..1]
 __global__ __launch_bounds__(1024) void sf_clean_scan_kernel(const FuseArgs *tab) {
-    __shared__ int wsum[16];
-    __shared__ int base;
     const FuseArgs &a = tab[blockIdx.x];  // one workgroup per map
-    const int n_blocks = (a.count + a.n_cand + SF_CLEAN_BLOCK - 1) / SF_CLEAN_BLOCK;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n_blocks; c0 += 1024) {
-        const int idx = c0 + tid;
-        const int v = idx < n_blocks ? a.block_counts[idx] : 0;
-        int incl = v;  // inclusive scan within the wave (DPP-free, shuffle based: not a hot loop)
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        if (idx < n_blocks) a.block_counts[idx] = off + incl - v;
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0;
-            for (int w = 0; w < 16; w++) t += wsum[w];
-            base += t;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
+    const int base = block_counts_scan(a.block_counts, (a.count + a.n_cand + SF_CLEAN_BLOCK - 1) / SF_CLEAN_BLOCK);
+    if (threadIdx.x == 0) {
         a.result[1] = base;
         a.result[0] = min(base, a.capacity);  // transform feedback stops at the end of its buffer
     }

@@ -31,9 +31,7 @@ static int check_filter(const sfw_filter *f) {
 // the checks every call makes before anything is launched
 static int check_maps(const char *what, sf_handle *h, int n, sf_map *const *maps, const sfw_filter *filters) {
     for (int q = 0; q < n; q++) {
-        if (!maps[q]) return fail(SF_ERR_ARG, std::string(what) + ": null map");
-        if (!maps[q]->h) return fail(SF_ERR_STATE, std::string(what) + ": the handle this map was created from has been destroyed");
-        if (maps[q]->h != h) return fail(SF_ERR_ARG, std::string(what) + ": a map belongs to the handle it was created from");
+        if (int e = check_map(what, h, maps[q])) return e;
         for (int r = 0; r < q; r++)
             if (maps[r] == maps[q]) return fail(SF_ERR_ARG, std::string(what) + ": the same map twice in one batch");
         if (int e = check_filter(filters + q)) return e;
@@ -85,16 +83,9 @@ static int partition(sf_handle *h, int n, sf_map *const *maps, const sfw_filter 
         a.result = h->res_dev + (size_t)q * 8;
         max_count = std::max(max_count, m->count);
     }
-    const size_t bytes = tab.size() * sizeof(WindowArgs);
-    if (h->tab_bytes < bytes) {
-        unsigned char *p = nullptr;
-        if (int e = dev_alloc(h, &p, bytes * 2)) return e;  // the old block is freed with the handle
-        h->tab_dev = p;
-        h->tab_bytes = bytes * 2;
-    }
-    h->tab_host.assign((const unsigned char *)tab.data(), (const unsigned char *)tab.data() + bytes);
-    HIP_TRY(hipMemcpyAsync(h->tab_dev, h->tab_host.data(), bytes, hipMemcpyHostToDevice, h->stream));
-    const WindowArgs *dev = (const WindowArgs *)h->tab_dev;
+    void *d = nullptr;
+    if (int e = upload_table(h, tab.data(), tab.size() * sizeof(WindowArgs), &d)) return e;
+    const WindowArgs *dev = (const WindowArgs *)d;
     if (max_count) {
         const dim3 grid((unsigned)((max_count + SFW_BLOCK - 1) / SFW_BLOCK), (unsigned)n);
         if (window_policy() >= 2)

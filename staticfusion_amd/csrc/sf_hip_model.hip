@@ -62,8 +62,14 @@ void invert_pose(const float pose[16], float out[16]) {  // (shared: sf_host.h)
     for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) out[r + 4 * c] = float(Ai[r * 4 + c]);
 }
-// device table for a batched launch: grows on demand, filled from a host copy that lives in the handle
-static int upload_table(sf_handle *h, const void *src, size_t bytes, void **dev) {
+int check_map(const char *what, const sf_handle *h, const sf_map *m) {  // (shared: sf_host.h)
+    if (!m) return fail(SF_ERR_ARG, std::string(what) + ": null map");
+    if (!m->h) return fail(SF_ERR_STATE, std::string(what) + ": the handle this map was created from has been destroyed");
+    if (m->h != h) return fail(SF_ERR_ARG, std::string(what) + ": a map belongs to the handle it was created from");
+    return SF_OK;
+}
+// device table for a batched launch: grows on demand, filled from a host copy that lives in the handle (shared: sf_host.h)
+int upload_table(sf_handle *h, const void *src, size_t bytes, void **dev) {
     if (h->tab_bytes < bytes) {
         unsigned char *q = nullptr;
         if (int e = dev_alloc(h, &q, bytes * 2)) return e;  // the old block is freed with the handle

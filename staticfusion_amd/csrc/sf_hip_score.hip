@@ -37,9 +37,7 @@ static int score(const char *what, ScoreForm form, sf_handle *h, int n, sf_map *
     std::vector<ViewJob> jobs((size_t)n);
     for (int q = 0; q < n; q++) {
         const sf_map *m = maps[q];
-        if (!m) return fail(SF_ERR_ARG, w + ": null map");
-        if (!m->h) return fail(SF_ERR_STATE, w + ": the handle this map was created from has been destroyed");
-        if (m->h != h) return fail(SF_ERR_ARG, w + ": a map belongs to the handle it was created from");
+        if (int e = check_map(what, h, m)) return e;
         if (int e = sfv_check_view(views + q)) return e;
         if (int e = check_params(params + q)) return e;
         if (form == FORM_STREAMS) {

@@ -161,9 +161,7 @@ static int render_maps(const char *what, sf_handle *h, int n, sf_map *const *map
     std::vector<ViewOut> outs((size_t)n);
     for (int q = 0; q < n; q++) {
         const sf_map *m = maps[q];
-        if (!m) return fail(SF_ERR_ARG, std::string(what) + ": null map");
-        if (!m->h) return fail(SF_ERR_STATE, std::string(what) + ": the handle this map was created from has been destroyed");
-        if (m->h != h) return fail(SF_ERR_ARG, std::string(what) + ": a map belongs to the handle it was created from");
+        if (int e = check_map(what, h, m)) return e;
         if (int e = check_view(views + q)) return e;
         jobs[(size_t)q] = ViewJob{m->buf[0], m->count, m->tick};
         outs[(size_t)q] = ViewOut{depth_out ? depth_out[q] : nullptr, rgb_out ? rgb_out[q] : nullptr, index_out ? index_out[q] : nullptr};
@@ -179,8 +177,8 @@ int sfv_check_view(const sfv_view *v) { return check_view(v); }
 
 int sfv_default_view(const sf_handle *h, sf_map *m, sfv_view *v) {
     if (!h || !v) return fail(SF_ERR_ARG, "sfv_default_view: null");
-    if (m && !m->h) return fail(SF_ERR_STATE, "sfv_default_view: the handle this map was created from has been destroyed");
-    if (m && m->h != h) return fail(SF_ERR_ARG, "sfv_default_view: a map belongs to the handle it was created from");
+    if (m)  // (a null map is allowed: the identity pose)
+        if (int e = check_map("sfv_default_view", h, m)) return e;
     sf_model_params p;
     if (int e = sf_default_model_params(h, &p)) return e;
     for (int k = 0; k < 16; k++) v->pose[k] = m ? m->pose[k] : ((k % 5 == 0) ? 1.f : 0.f);

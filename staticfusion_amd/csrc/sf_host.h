@@ -3,7 +3,8 @@
 //   sf_hip.hip         handle lifetime, parameters, the builds of the frame kernel, launch()
 //   sf_hip_solver.hip  images in, frames (one or several per launch), results and debug planes out, measurement support
 //   sf_hip_input.hip   the input stage: loader decimation / RGB -> intensity, bilateral depth filter (sf_input.h)
-//   sf_hip_model.hip   frame-to-model prediction and the surfel map without OpenGL (sf_predict.h, sf_fusion.h)
+//   sf_hip_model.hip   frame-to-model prediction and the surfel map without OpenGL (sf_predict.h, sf_fusion.h); the map
+//                      check and the table upload of every part that takes maps (check_map, upload_table)
 //   sf_hip_migrate.hip single streams between handles, to and from host memory, back to constructor state (sf_migrate.h;
 //                      its interface is include/sf_migrate.h, symbols sfm_*)
 //   sf_hip_map_window.hip  bounded maps: count, cull, extract, page out, append (sf_map_window.h; its interface is
@@ -253,5 +254,9 @@ SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  //
 SF_INTERNAL int input_alloc(sf_handle *h);                                    // sf_hip_input.hip: buffers of the input stage, on first use
 SF_INTERNAL void orphan_maps(sf_handle *h);                                   // sf_hip_model.hip: sf_destroy releases the handle's maps
 SF_INTERNAL void invert_pose(const float pose[16], float out[16]);            // sf_hip_model.hip: t_inv of the prediction, the fusion and the views
+// sf_hip_model.hip: a map handed to `what` beside h is not null (SF_ERR_ARG), not orphaned (SF_ERR_STATE) and h's own (SF_ERR_ARG)
+SF_INTERNAL int check_map(const char *what, const sf_handle *h, const sf_map *m);
+// sf_hip_model.hip: the table of a batched launch into h->tab_dev (grown on demand; it stays there for later launches of the call)
+SF_INTERNAL int upload_table(sf_handle *h, const void *src, size_t bytes, void **dev);
 SF_INTERNAL void migrate_release(sf_handle *h);                               // sf_hip_migrate.hip: sf_destroy releases the pinned tables and events
 }

@@ -72,35 +72,9 @@ __global__ __launch_bounds__(SFW_BLOCK) void sfw_flag_kernel(const WindowArgs *t
 }
 // exclusive scan of the block counts in place (one workgroup per map, 1024 counts per trip), the total into result[0]
 __global__ __launch_bounds__(1024) void sfw_scan_kernel(const WindowArgs *tab) {
-    __shared__ int wsum[16];
-    __shared__ int base;
     const WindowArgs &a = tab[blockIdx.x];
-    const int n_blocks = (a.count + SFW_BLOCK - 1) / SFW_BLOCK;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n_blocks; c0 += 1024) {
-        const int idx = c0 + tid;
-        const int v = idx < n_blocks ? a.block_counts[idx] : 0;
-        int incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++) off += wsum[w];
-        if (idx < n_blocks) a.block_counts[idx] = off + incl - v;
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0;
-            for (int w = 0; w < 16; w++) t += wsum[w];
-            base += t;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) a.result[0] = base;
+    const int base = block_counts_scan(a.block_counts, (a.count + SFW_BLOCK - 1) / SFW_BLOCK);
+    if (threadIdx.x == 0) a.result[0] = base;
 }
 // element e with r selected elements before it goes to r if selected, to k + (e - r) otherwise: both parts keep their order
 template <bool NT>

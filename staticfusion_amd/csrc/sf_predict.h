@@ -10,9 +10,11 @@
 // (gl_FragDepth is a positive float: its bit pattern is monotonic; the index makes the earlier surfel win a
 // tie, as in-order GL_LESS does). A second kernel re-evaluates the winning fragment per pixel and runs the
 // per-pixel fill-in / extraction. Both confidence levels are rendered by the same pass (two key buffers).
+// The camera transform, the sprite extent, the fragment test and the key are those of sf_surfel_geom.h, which the
+// views and the scores share; the cull of splat.vert:57 is stated here.
 // Every float expression repeats the shader's association; no contraction: bit-identical to the CPU oracle.
 #pragma once
-#include "sf_device_common.h"
+#include "sf_surfel_geom.h"
 
 struct PredictArgs {
     const float *surfels;  // count x 12
@@ -32,54 +34,23 @@ struct PredictArgs {
 
 #define SF_PRED_EMPTY 0xffffffffffffffffull
 
-struct PV3 { float x, y, z; };
-__device__ __forceinline__ float pdot(PV3 a, PV3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ PV3 padd(PV3 a, PV3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ PV3 psub(PV3 a, PV3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ PV3 pmul(PV3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ PV3 pnormalize(PV3 a) {
-    const float n = sqrtf(pdot(a, a));
-    return {a.x / n, a.y / n, a.z / n};
-}
-__device__ __forceinline__ PV3 pcross(PV3 a, PV3 b) { return {a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
-
-// camera-frame position, normal and radius of surfel s (splat.vert:55,68); false if culled by :57
+// camera-frame position, normal and radius of surfel s; false if culled by splat.vert:57, before its normal is loaded.
+// Every output is set whenever the surfel passes the cull: resolve_pixel ignores the result for a surfel that won a pixel.
 __device__ __forceinline__ bool surfel_to_camera(const PredictArgs &a, int s, float conf_threshold, PV3 &h, PV3 &n, float &rad) {
-    const auto q = as_global(a.surfels) + (size_t)s * 12;  // typed global pointer: global_load, not flat_load
-    const float *T = a.t_inv;
-    const PV3 vp{q[0], q[1], q[2]};
-    const float conf = q[3], tlast = q[7];
-    h = PV3{T[0] * vp.x + T[4] * vp.y + T[8] * vp.z + T[12], T[1] * vp.x + T[5] * vp.y + T[9] * vp.z + T[13],
-            T[2] * vp.x + T[6] * vp.y + T[10] * vp.z + T[14]};
+    float conf, tlast;
+    const auto q = surfel_record(a, s);
+    h = surfel_camera_position(a, q, conf, tlast);
     if (h.z > a.max_depth || h.z < 0.4f || conf < conf_threshold || float(a.time) - tlast > float(a.time_delta) || tlast > float(a.max_time))
         return false;
-    const PV3 nin{q[8], q[9], q[10]};
-    n = pnormalize(PV3{T[0] * nin.x + T[4] * nin.y + T[8] * nin.z, T[1] * nin.x + T[5] * nin.y + T[9] * nin.z,
-                       T[2] * nin.x + T[6] * nin.y + T[10] * nin.z});
-    rad = q[11];
+    n = surfel_camera_normal(a, q, rad);
     return true;
-}
-
-// combo_splat.frag:37-49,63 for the fragment at pixel (i, j); false = discard
-__device__ __forceinline__ bool surfel_fragment(const PredictArgs &a, PV3 h, PV3 n, float rad, int i, int j, float &z, float &depth) {
-    // the view ray of the pixel (combo_splat.frag:37-39) does not depend on the surfel: five divisions and a square root per
-    // fragment become one 16-byte load from a table built with the same expression (sf_predict_rays_kernel)
-    const vfloat4 lr = as_global(a.rays)[j + (size_t)i * a.rows];
-    const PV3 l{lr.x, lr.y, lr.z};
-    const PV3 corrected = pmul(l, pdot(h, n) / pdot(l, n));
-    const PV3 diff = psub(corrected, h);
-    if (pdot(diff, diff) > rad * rad) return false;
-    z = corrected.z;
-    depth = (corrected.z / (2.f * a.max_depth)) + 0.5f;
-    return depth >= 0.f && depth < 1.f;  // depth range clip, and GL_LESS against the cleared depth 1.0: a fragment AT 1.0 fails
 }
 
 __global__ __launch_bounds__(256) void sf_predict_rays_kernel(vfloat4 *rays, int rows, int cols, float cx, float cy, float fx, float fy) {
     const int idx = blockIdx.x * 256 + threadIdx.x;  // j + i * rows
     if (idx >= rows * cols) return;
     const int i = idx / rows, j = idx - i * rows;
-    const float fx_ = float(i) + 0.5f, fy_ = float(j) + 0.5f;  // gl_FragCoord
-    const PV3 l = pnormalize(PV3{(fx_ - cx) / fx, (fy_ - cy) / fy, 1.0f});
+    const PV3 l = surfel_view_ray(i, j, cx, cy, fx, fy);
     rays[idx] = vfloat4{l.x, l.y, l.z, 0.f};
 }
 // Every kernel takes a TABLE of PredictArgs and works on entry blockIdx.y (one launch renders the maps of many streams).
@@ -118,51 +89,9 @@ __global__ __launch_bounds__(SF_SPLAT_NT) void sf_predict_splat_kernel(const Pre
     int i0 = 0, i1 = -1, j0 = 0, j1 = -1;
     if (valid) {
         high = !(as_global(a.surfels)[(size_t)s * 12 + 3] < a.conf_high);
-        const float fcols = float(a.cols), frows = float(a.rows);
-        const float ndc_x = ((((a.fx * h.x) / h.z) + a.cx) - (fcols * 0.5f)) / (fcols * 0.5f);
-        const float ndc_y = ((((a.fy * h.y) / h.z) + a.cy) - (frows * 0.5f)) / (frows * 0.5f);
-        valid = (ndc_x >= -1.f && ndc_x <= 1.f && ndc_y >= -1.f && ndc_y <= 1.f);
-        if (valid) {
-            const float xw = (ndc_x + 1.f) * (fcols * 0.5f), yw = (ndc_y + 1.f) * (frows * 0.5f);
-            const PV3 x1 = pmul(pmul(pnormalize(PV3{n.y - n.z, -n.x, n.x}), rad), 1.41421356f);
-            const PV3 y1 = pcross(n, x1);
-            const PV3 c1 = padd(h, x1), c2 = padd(h, y1), c3 = psub(h, y1), c4 = psub(h, x1);
-            const float p1x = ((a.fx * c1.x) / c1.z) + a.cx, p1y = ((a.fy * c1.y) / c1.z) + a.cy;
-            const float p2x = ((a.fx * c2.x) / c2.z) + a.cx, p2y = ((a.fy * c2.y) / c2.z) + a.cy;
-            const float p3x = ((a.fx * c3.x) / c3.z) + a.cx, p3y = ((a.fy * c3.y) / c3.z) + a.cy;
-            const float p4x = ((a.fx * c4.x) / c4.z) + a.cx, p4y = ((a.fy * c4.y) / c4.z) + a.cy;
-            const float xDiff = fabsf(fmaxf(p1x, fmaxf(p2x, fmaxf(p3x, p4x))) - fminf(p1x, fminf(p2x, fminf(p3x, p4x))));
-            const float yDiff = fabsf(fmaxf(p1y, fmaxf(p2y, fmaxf(p3y, p4y))) - fminf(p1y, fminf(p2y, fminf(p3y, p4y))));
-            const float size = fmaxf(0.f, fmaxf(xDiff, yDiff));
-            valid = size > 0.f;
-            if (valid) {
-                const float half = size * 0.5f;
-                i0 = max(0, (int)ceilf(xw - half - 0.5f)); i1 = min(a.cols - 1, (int)floorf(xw + half - 0.5f));
-                j0 = max(0, (int)ceilf(yw - half - 0.5f)); j1 = min(a.rows - 1, (int)floorf(yw + half - 0.5f));
-                // The sprite is a SQUARE of the longer extent (splat.vert:85), but a fragment survives only inside the disc
-                // (combo_splat.frag:47), and the disc lies inside the diamond whose corners were just projected: pixels outside
-                // their bounding rectangle (+ 1 pixel against rounding at the rim) would be discarded anyway -- skip them.
-                const float xlo = fminf(p1x, fminf(p2x, fminf(p3x, p4x))), xhi = fmaxf(p1x, fmaxf(p2x, fmaxf(p3x, p4x)));
-                const float ylo = fminf(p1y, fminf(p2y, fminf(p3y, p4y))), yhi = fmaxf(p1y, fmaxf(p2y, fmaxf(p3y, p4y)));
-                i0 = max(i0, (int)floorf(xlo - 1.5f)); i1 = min(i1, (int)ceilf(xhi + 0.5f));
-                j0 = max(j0, (int)floorf(ylo - 1.5f)); j1 = min(j1, (int)ceilf(yhi + 0.5f));
-                valid = i0 <= i1 && j0 <= j1;
-            }
-        }
+        valid = surfel_sprite(a, h, n, rad, i0, i1, j0, j1);
     }
-    // bounding box of the workgroup's sprites
-    if (tid == 0) {
-        bb[0] = bb[1] = 0x7fffffff;
-        bb[2] = bb[3] = -1;
-    }
-    __syncthreads();
-    if (valid) {
-        atomicMin(&bb[0], i0);
-        atomicMin(&bb[1], j0);
-        atomicMax(&bb[2], i1);
-        atomicMax(&bb[3], j1);
-    }
-    __syncthreads();
+    workgroup_sprite_box(bb, valid, i0, i1, j0, j1);
     const int bi0 = bb[0], bj0 = bb[1], bw = bb[2] - bi0 + 1, bh = bb[3] - bj0 + 1;
     if (bw <= 0 || bh <= 0) return;  // nothing to draw (uniform: read from LDS after the barrier)
     const bool tiled = bw * bh <= SF_SPLAT_TILE;
@@ -181,7 +110,7 @@ __global__ __launch_bounds__(SF_SPLAT_NT) void sf_predict_splat_kernel(const Pre
             for (int j = j0; j <= j1; j++) {  // neighbours) and the inner loop touch neighbouring words
                 float z, depth;
                 if (!surfel_fragment(a, h, n, rad, i, j, z, depth)) continue;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)s;
+                const unsigned long long key = surfel_key(depth, s);
                 if (tiled) {
                     const int t = wide ? (j - bj0) * bw + (i - bi0) : (i - bi0) * bh + (j - bj0);
                     atomicMin(&tile[0][t], key);

@@ -57,10 +57,10 @@ __global__ __launch_bounds__(SFS_NT) void sfs_score_kernel(const ViewArgs *vtab,
                 drawn = true;
                 const int s = (int)(unsigned)(key & 0xffffffffull);
                 const int x = idx / a.rows, y = idx - x * a.rows;
-                VV3 h, n;
+                PV3 h, n;
                 float rad, depth;
                 sfv_to_camera(a, s, h, n, rad);
-                sfv_fragment(a, h, n, rad, x, y, zm, depth);
+                surfel_fragment(a, h, n, rad, x, y, zm, depth);
                 c = (unsigned)(int)as_global(a.surfels)[(size_t)s * 12 + 4] & 0xffffffu;  // color.glsl decodeColor
             }
         }

@@ -1,9 +1,9 @@
 // sf_view.h — device code of include/sf_view.h (host side: sf_hip_view.hip): a surfel buffer drawn from any pose, with any
 // pinhole intrinsics, at any size, into a depth, a colour and an index image. The geometry is ONE target of
-// IndexMap::combinedPredict exactly as sf_predict.h states it (splat.vert, combo_splat.frag): visibility is one 64-bit
-// atomicMin per fragment on (bits of gl_FragDepth) << 32 | surfel index, so the images do not depend on the execution
-// order. The argument table, the camera transform, the sprite extent and the fragment test are in sf_view_common.h, which
-// the score kernel (sf_score.h) shares; the kernels below are defined once, in the translation unit of sf_hip_view.hip.
+// IndexMap::combinedPredict (splat.vert, combo_splat.frag), the very functions the prediction draws with (sf_surfel_geom.h):
+// visibility is one 64-bit atomicMin per fragment on (bits of gl_FragDepth) << 32 | surfel index, so the images do not
+// depend on the execution order. The argument table and the cull of a view are in sf_view_common.h, which the score kernel
+// (sf_score.h) shares; the kernels below are defined once, in the translation unit of sf_hip_view.hip.
 //
 // Four launches serve a whole batch of views (table entry blockIdx.y, like PredictArgs / WindowArgs): clear, splat (a lane
 // per surfel), large sprites (a wave per listed surfel), resolve (a lane per pixel). A fifth, in front, builds the view-ray
@@ -30,8 +30,7 @@ __global__ __launch_bounds__(256) void sfv_rays_kernel(const ViewRayArgs *tab) {
     const int idx = blockIdx.x * 256 + threadIdx.x;  // j + i * rows
     if (idx >= a.rows * a.cols) return;
     const int i = idx / a.rows, j = idx - i * a.rows;
-    const float fx_ = float(i) + 0.5f, fy_ = float(j) + 0.5f;  // gl_FragCoord
-    const VV3 l = vnormalize(VV3{(fx_ - a.cx) / a.fx, (fy_ - a.cy) / a.fy, 1.0f});
+    const PV3 l = surfel_view_ray(i, j, a.cx, a.cy, a.fx, a.fy);
     a.rays[idx] = vfloat4{l.x, l.y, l.z, 0.f};
 }
 
@@ -52,7 +51,7 @@ __global__ __launch_bounds__(SFV_SPLAT_NT) void sfv_splat_kernel(const ViewArgs 
     if ((int)blockIdx.x * SFV_SPLAT_NT >= a.count) return;  // a workgroup of a larger map of the batch
     const int tid = threadIdx.x;
     const int s = blockIdx.x * SFV_SPLAT_NT + tid;
-    VV3 h{0.f, 0.f, 1.f}, n{0.f, 0.f, 1.f};
+    PV3 h{0.f, 0.f, 1.f}, n{0.f, 0.f, 1.f};
     float rad = 0.f;
     int i0 = 0, i1 = -1, j0 = 0, j1 = -1;
     bool valid = s < a.count && sfv_sprite(a, s, h, n, rad, i0, i1, j0, j1);
@@ -61,18 +60,7 @@ __global__ __launch_bounds__(SFV_SPLAT_NT) void sfv_splat_kernel(const ViewArgs 
         if (slot < a.count) a.large_list[slot] = s;  // (always: a surfel is listed once)
         valid = false;
     }
-    if (tid == 0) {
-        bb[0] = bb[1] = 0x7fffffff;
-        bb[2] = bb[3] = -1;
-    }
-    __syncthreads();
-    if (valid) {
-        atomicMin(&bb[0], i0);
-        atomicMin(&bb[1], j0);
-        atomicMax(&bb[2], i1);
-        atomicMax(&bb[3], j1);
-    }
-    __syncthreads();
+    workgroup_sprite_box(bb, valid, i0, i1, j0, j1);
     const int bi0 = bb[0], bj0 = bb[1], bw = bb[2] - bi0 + 1, bh = bb[3] - bj0 + 1;
     if (bw <= 0 || bh <= 0) return;  // nothing to draw (uniform: read from LDS after the barrier)
     const bool tiled = (long long)bw * bh <= SFV_SPLAT_TILE;
@@ -85,8 +73,8 @@ __global__ __launch_bounds__(SFV_SPLAT_NT) void sfv_splat_kernel(const ViewArgs 
         for (int i = i0; i <= i1; i++)
             for (int j = j0; j <= j1; j++) {
                 float z, depth;
-                if (!sfv_fragment(a, h, n, rad, i, j, z, depth)) continue;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)s;
+                if (!surfel_fragment(a, h, n, rad, i, j, z, depth)) continue;
+                const unsigned long long key = surfel_key(depth, s);
                 if (tiled) {
                     const int t = wide ? (j - bj0) * bw + (i - bi0) : (i - bi0) * bh + (j - bj0);
                     atomicMin(&tile[t], key);
@@ -115,7 +103,7 @@ __global__ __launch_bounds__(SFV_LARGE_NT) void sfv_large_kernel(const ViewArgs 
     for (int e = (int)blockIdx.x * (SFV_LARGE_NT / 64) + (int)(threadIdx.x >> 6); e < n_listed; e += waves) {
         const int s = __builtin_amdgcn_readfirstlane(a.large_list[e]);
         if (s < 0 || s >= a.count) continue;
-        VV3 h, n;
+        PV3 h, n;
         float rad;
         int i0, i1, j0, j1;
         if (!sfv_sprite(a, s, h, n, rad, i0, i1, j0, j1)) continue;  // (it was drawn when it was listed)
@@ -124,8 +112,8 @@ __global__ __launch_bounds__(SFV_LARGE_NT) void sfv_large_kernel(const ViewArgs 
         int i = i0 + lane / hgt, j = j0 + lane % hgt;
         for (int q = lane; q < total; q += 64) {
             float z, depth;
-            if (sfv_fragment(a, h, n, rad, i, j, z, depth)) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)s;
+            if (surfel_fragment(a, h, n, rad, i, j, z, depth)) {
+                const unsigned long long key = surfel_key(depth, s);
                 __hip_atomic_fetch_min(as_global(a.keys) + (j + (size_t)i * a.rows), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             i += di;
@@ -162,10 +150,10 @@ __global__ __launch_bounds__(256) void sfv_resolve_kernel(const ViewArgs *tab) {
         int s = -1;
         if (key != SFV_EMPTY) {
             s = (int)(unsigned)(key & 0xffffffffull);
-            VV3 h, n;
+            PV3 h, n;
             float rad, depth;
             sfv_to_camera(a, s, h, n, rad);
-            sfv_fragment(a, h, n, rad, x, y, z, depth);
+            surfel_fragment(a, h, n, rad, x, y, z, depth);
             if (a.shade == 1) {  // SFV_SHADE_NORMAL
                 const float v[3] = {n.x, n.y, n.z};
 #pragma unroll

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
+from ._companion import binder, map_array, one_solver
 
 _H = C.c_void_p
 _ip = C.POINTER(C.c_int32)
@@ -48,41 +49,7 @@ def Filter(min_confidence=0.0, max_age=-1, centre=None, radius=0.0, invert=False
     return SfwFilter(float(min_confidence), int(max_age), (C.c_float * 3)(*c), float(radius), int(bool(invert)), 0)
 
 
-class _Binding:
-    def __init__(self, api):
-        if api.prefix != "sf_":
-            raise SfError("map windows are implemented by the HIP library only (this binding has the prefix %r)" % api.prefix)
-        self.api = api
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(api.lib, name)  # AttributeError if the library lacks the symbol
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name[4:], fn)
-        if self.version() != VERSION:
-            raise SfError("%s: sfw_version %d, this binding restates %d" % (api.lib_path, self.version(), VERSION))
-        if self.filter_bytes() != C.sizeof(SfwFilter):
-            raise SfError("%s: sfw_filter has %d bytes, this binding's %d" % (api.lib_path, self.filter_bytes(), C.sizeof(SfwFilter)))
-
-    def check(self, code, what):
-        if code != 0:
-            msg = self.api.last_error()
-            raise SfError("sfw_%s failed with %d: %s" % (what, code, msg.decode() if msg else ""))
-
-
-_bound = {}
-
-
-def _bind(api):
-    b = _bound.get(api.lib_path)
-    if b is None:
-        b = _bound[api.lib_path] = _Binding(api)
-    return b
-
-
-def _product():
-    from . import load
-
-    return _bind(load())
+_bind, _product = binder("sfw_", "map windows are", SIGNATURES, VERSION, [("filter_bytes", "sfw_filter", C.sizeof(SfwFilter))])
 
 
 def version():
@@ -109,9 +76,8 @@ def _batch(maps, filters):
     if len(maps) != len(filters):
         raise SfError("%d maps and %d filters" % (len(maps), len(filters)))
     n = len(maps)
-    if n and any(m.solver is not maps[0].solver for m in maps):
-        raise SfError("the maps of one call belong to one solver")
-    return n, (C.c_void_p * max(n, 1))(*[m.m.value for m in maps]), (SfwFilter * max(n, 1))(*filters), (C.c_int32 * max(n, 1))()
+    one_solver(maps)
+    return n, map_array(maps), (SfwFilter * max(n, 1))(*filters), (C.c_int32 * max(n, 1))()
 
 
 def count(maps, filters):

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
+from ._companion import binder, map_array, one_solver, ptr_array
 from .view import SfvView
 
 _H = C.c_void_p
@@ -52,43 +53,8 @@ def Params(tol_abs=0.02, tol_rel=0.01, max_residual=8.0, b_min=0.5, use_grey=Tru
     return SfsParams(float(tol_abs), float(tol_rel), float(max_residual), float(b_min), int(use_grey), int(use_b))
 
 
-class _Binding:
-    def __init__(self, api):
-        if api.prefix != "sf_":
-            raise SfError("scores are implemented by the HIP library only (this binding has the prefix %r)" % api.prefix)
-        self.api = api
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(api.lib, name)  # AttributeError if the library lacks the symbol
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name[4:], fn)
-        if self.version() != VERSION:
-            raise SfError("%s: sfs_version %d, this binding restates %d" % (api.lib_path, self.version(), VERSION))
-        if self.params_bytes() != C.sizeof(SfsParams):
-            raise SfError("%s: sfs_params has %d bytes, this binding's %d" % (api.lib_path, self.params_bytes(), C.sizeof(SfsParams)))
-        if self.score_bytes() != SCORE_DTYPE.itemsize:
-            raise SfError("%s: sfs_score has %d bytes, this binding's %d" % (api.lib_path, self.score_bytes(), SCORE_DTYPE.itemsize))
-
-    def check(self, code, what):
-        if code != 0:
-            msg = self.api.last_error()
-            raise SfError("sfs_%s failed with %d: %s" % (what, code, msg.decode() if msg else ""))
-
-
-_bound = {}
-
-
-def _bind(api):
-    b = _bound.get(api.lib_path)
-    if b is None:
-        b = _bound[api.lib_path] = _Binding(api)
-    return b
-
-
-def _product():
-    from . import load
-
-    return _bind(load())
+_bind, _product = binder("sfs_", "scores are", SIGNATURES, VERSION,
+                         [("params_bytes", "sfs_params", C.sizeof(SfsParams)), ("score_bytes", "sfs_score", SCORE_DTYPE.itemsize)])
 
 
 def version():
@@ -126,8 +92,7 @@ def _entries(maps, views, params):
     params = [params] * n if isinstance(params, SfsParams) else list(params)
     if len(params) != n:
         raise SfError("%d maps and %d parameter sets" % (n, len(params)))
-    if n and any(m.solver is not maps[0].solver for m in maps):
-        raise SfError("the maps of one call belong to one solver")
+    one_solver(maps)
     return maps, views, params, n
 
 
@@ -165,8 +130,7 @@ def score_streams(maps, views, streams, params=None, classes=False):
         return _finish(rec, [] if classes else None)
     b = _bind(maps[0].api)
     imgs, cp = _class_images(views, classes)
-    mp = (C.c_void_p * n)(*[m.m.value for m in maps])
-    b.check(b.score_streams(maps[0].solver.h, n, mp, (SfvView * n)(*views), (C.c_int32 * n)(*streams), (SfsParams * n)(*params), rec.ctypes.data, cp),
+    b.check(b.score_streams(maps[0].solver.h, n, map_array(maps), (SfvView * n)(*views), (C.c_int32 * n)(*streams), (SfsParams * n)(*params), rec.ctypes.data, cp),
             "score_streams")
     return _finish(rec, imgs)
 
@@ -184,12 +148,6 @@ def _column_major(images, views, what):
     return out
 
 
-def _ptr_array(arrays):
-    if arrays is None:
-        return None
-    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
-
-
 def score_images(maps, views, depth, grey=None, b=None, params=None, classes=False):
     """the same with frames in host memory: depth[q], grey[q], b[q] are (rows, cols) float32 arrays of the size of views[q]
     (grey and b: a list that may hold None, or None)"""
@@ -204,9 +162,8 @@ def score_images(maps, views, depth, grey=None, b=None, params=None, classes=Fal
     if len(d) != n or any(a is None for a in d):
         raise SfError("one depth image per entry")
     imgs, cp = _class_images(views, classes)
-    mp = (C.c_void_p * n)(*[m.m.value for m in maps])
-    bd.check(bd.score_images(maps[0].solver.h, n, mp, (SfvView * n)(*views), _ptr_array(d), _ptr_array(g), _ptr_array(w), (SfsParams * n)(*params),
-                             rec.ctypes.data, cp), "score_images")
+    bd.check(bd.score_images(maps[0].solver.h, n, map_array(maps), (SfvView * n)(*views), ptr_array(d, n), ptr_array(g, n), ptr_array(w, n),
+                             (SfsParams * n)(*params), rec.ctypes.data, cp), "score_images")
     return _finish(rec, imgs)
 
 
@@ -217,10 +174,6 @@ def score_images_device(maps, views, depth_ptrs, grey_ptrs, b_ptrs, params, scor
     if n == 0:
         return
     b = _bind(maps[0].api)
-
-    def arr(p):
-        return None if p is None else (C.c_void_p * n)(*[None if x is None else int(x) for x in p])
-
-    mp = (C.c_void_p * n)(*[m.m.value for m in maps])
-    b.check(b.score_images_device(maps[0].solver.h, n, mp, (SfvView * n)(*views), arr(depth_ptrs), arr(grey_ptrs), arr(b_ptrs), (SfsParams * n)(*params),
-                                  C.c_void_p(int(scores_ptr)), arr(class_ptrs)), "score_images_device")
+    b.check(b.score_images_device(maps[0].solver.h, n, map_array(maps), (SfvView * n)(*views), ptr_array(depth_ptrs, n), ptr_array(grey_ptrs, n),
+                                  ptr_array(b_ptrs, n), (SfsParams * n)(*params), C.c_void_p(int(scores_ptr)), ptr_array(class_ptrs, n)),
+            "score_images_device")

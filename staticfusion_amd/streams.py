@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
+from ._companion import binder
 
 _H = C.c_void_p
 _ip = C.POINTER(C.c_int32)
@@ -27,39 +28,7 @@ SIGNATURES = {
 VERSION = 1  # sfm_version() of the header this table restates
 
 
-class _Binding:
-    def __init__(self, api):
-        if api.prefix != "sf_":
-            raise SfError("stream migration is implemented by the HIP library only (this binding has the prefix %r)" % api.prefix)
-        self.api = api
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(api.lib, name)  # AttributeError if the library lacks the symbol
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name[4:], fn)
-        if self.version() != VERSION:
-            raise SfError("%s: sfm_version %d, this binding restates %d" % (api.lib_path, self.version(), VERSION))
-
-    def check(self, code, what):
-        if code != 0:
-            msg = self.api.last_error()
-            raise SfError("sfm_%s failed with %d: %s" % (what, code, msg.decode() if msg else ""))
-
-
-_bound = {}
-
-
-def _bind(api):
-    b = _bound.get(api.lib_path)
-    if b is None:
-        b = _bound[api.lib_path] = _Binding(api)
-    return b
-
-
-def _product():
-    from . import load
-
-    return _bind(load())
+_bind, _product = binder("sfm_", "stream migration is", SIGNATURES, VERSION)
 
 
 def _ints(a):

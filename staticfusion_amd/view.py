@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
+from ._companion import binder, map_array, one_solver, ptr_array
 
 _H = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -70,41 +71,7 @@ def look_at(eye, target, up=(0.0, -1.0, 0.0)):
     return T
 
 
-class _Binding:
-    def __init__(self, api):
-        if api.prefix != "sf_":
-            raise SfError("views are implemented by the HIP library only (this binding has the prefix %r)" % api.prefix)
-        self.api = api
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(api.lib, name)  # AttributeError if the library lacks the symbol
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name[4:], fn)
-        if self.version() != VERSION:
-            raise SfError("%s: sfv_version %d, this binding restates %d" % (api.lib_path, self.version(), VERSION))
-        if self.view_bytes() != C.sizeof(SfvView):
-            raise SfError("%s: sfv_view has %d bytes, this binding's %d" % (api.lib_path, self.view_bytes(), C.sizeof(SfvView)))
-
-    def check(self, code, what):
-        if code != 0:
-            msg = self.api.last_error()
-            raise SfError("sfv_%s failed with %d: %s" % (what, code, msg.decode() if msg else ""))
-
-
-_bound = {}
-
-
-def _bind(api):
-    b = _bound.get(api.lib_path)
-    if b is None:
-        b = _bound[api.lib_path] = _Binding(api)
-    return b
-
-
-def _product():
-    from . import load
-
-    return _bind(load())
+_bind, _product = binder("sfv_", "views are", SIGNATURES, VERSION, [("view_bytes", "sfv_view", C.sizeof(SfvView))])
 
 
 def version():
@@ -136,12 +103,6 @@ def _images(views, depth, rgb, index):
     return d, c, i
 
 
-def _ptrs(arrays):
-    if all(a is None for a in arrays):
-        return None
-    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
-
-
 def render(maps, views, depth=True, rgb=True, index=True):
     """views[q] of maps[q] in one call (the same map may appear any number of times; the views may differ in size). Returns a
     list of dicts with the images asked for: depth (rows, cols) float32, rgb (rows, cols, 3) uint8, index (rows, cols) int32."""
@@ -151,12 +112,11 @@ def render(maps, views, depth=True, rgb=True, index=True):
     n = len(maps)
     if n == 0:
         return []
-    if any(m.solver is not maps[0].solver for m in maps):
-        raise SfError("the maps of one call belong to one solver")
+    one_solver(maps)
     b = _bind(maps[0].api)
     d, c, i = _images(views, depth, rgb, index)
-    mp = (C.c_void_p * n)(*[m.m.value for m in maps])
-    b.check(b.render_maps(maps[0].solver.h, n, mp, (SfvView * n)(*views), _ptrs(d), _ptrs(c), _ptrs(i)), "render_maps")
+    b.check(b.render_maps(maps[0].solver.h, n, map_array(maps), (SfvView * n)(*views), ptr_array(d if depth else None, n),
+                          ptr_array(c if rgb else None, n), ptr_array(i if index else None, n)), "render_maps")
     return [{k: a[q] for k, a in (("depth", d), ("rgb", c), ("index", i)) if a[q] is not None} for q in range(n)]
 
 
@@ -167,12 +127,8 @@ def render_device(maps, views, depth_ptrs=None, rgb_ptrs=None, index_ptrs=None):
     if n == 0:
         return
     b = _bind(maps[0].api)
-
-    def arr(p):
-        return None if p is None else (C.c_void_p * n)(*[None if x is None else int(x) for x in p])
-
-    mp = (C.c_void_p * n)(*[m.m.value for m in maps])
-    b.check(b.render_maps_device(maps[0].solver.h, n, mp, (SfvView * n)(*views), arr(depth_ptrs), arr(rgb_ptrs), arr(index_ptrs)), "render_maps_device")
+    b.check(b.render_maps_device(maps[0].solver.h, n, map_array(maps), (SfvView * n)(*views), ptr_array(depth_ptrs, n), ptr_array(rgb_ptrs, n),
+                                 ptr_array(index_ptrs, n)), "render_maps_device")
 
 
 def render_surfels(solver, surfels, view, tick=1, depth=True, rgb=True, index=True):
