@@ -242,22 +242,7 @@ void sf_destroy(sf_handle *h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     orphan_maps(h);  // maps outliving their handle: their memory is freed now, every later call on them fails cleanly
-    migrate_release(h);
-    for (void *p : h->allocs) (void)hipFree(p);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->evk0) (void)hipEventDestroy(h->evk0);
-    if (h->evk1) (void)hipEventDestroy(h->evk1);
-    if (h->seq_index_host) (void)hipHostFree(h->seq_index_host);
-    if (h->d_multi_index) (void)hipFree(h->d_multi_index);
-    if (h->h_multi_index) (void)hipHostFree(h->h_multi_index);
-    if (h->d_traj) (void)hipFree(h->d_traj);
-    for (auto &e : h->seq_done)
-        if (e) (void)hipEventDestroy(e);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->copy_done) (void)hipEventDestroy(h->copy_done);
-    if (h->compute_done) (void)hipEventDestroy(h->compute_done);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    h->own.release_all();
     delete h;
 }
 
@@ -392,12 +377,9 @@ int sf_create_ex(const sf_params *p, int rows, int cols, int batch, int device, 
         h->cluster_grid = 8 * streams_per_xcd * G;
         slots = (size_t)batch * (1 + G);
     }
-    HIP_OR_FREE(hipStreamCreate(&h->own_stream));
+    TRY_OR_FREE(h->own.stream(&h->own_stream, hipStreamDefault));
     h->stream = h->own_stream;
-    HIP_OR_FREE(hipEventCreate(&h->ev0));
-    HIP_OR_FREE(hipEventCreate(&h->ev1));
-    HIP_OR_FREE(hipEventCreate(&h->evk0));
-    HIP_OR_FREE(hipEventCreate(&h->evk1));
+    for (hipEvent_t *ev : {&h->ev0, &h->ev1, &h->evk0, &h->evk1}) TRY_OR_FREE(h->own.event(ev, hipEventDefault));
 
     const size_t B = batch, NT = k.n_tot, N0 = k.n0;
     for (int c = 0; c < 2; c++) {  // depth, intensity; xx / yy are recomputed (level_coord), their table entries stay null

@@ -9,10 +9,19 @@ extern "C" {
 int input_alloc(sf_handle *h) {
     if (h->in_depth_mm) return SF_OK;
     const size_t n = (size_t)h->k.n0 * h->k.batch;
-    if (int e = dev_alloc(h, &h->in_depth_mm, n)) return e;
-    if (int e = dev_alloc(h, &h->in_filtered_mm, n)) return e;
-    if (int e = dev_alloc(h, &h->in_depth_metric, n)) return e;
-    if (int e = dev_alloc(h, &h->in_color, n * 3)) return e;
+    SfOwner g;  // a group (sf_resources.h): in_depth_mm is set only when all four blocks exist
+    uint16_t *depth_mm = nullptr, *filtered_mm = nullptr;
+    float *depth_metric = nullptr;
+    uint8_t *color = nullptr;
+    if (int e = g.device(&depth_mm, n)) return e;
+    if (int e = g.device(&filtered_mm, n)) return e;
+    if (int e = g.device(&depth_metric, n)) return e;
+    if (int e = g.device(&color, n * 3)) return e;
+    h->own.adopt(g);
+    h->in_depth_mm = depth_mm;
+    h->in_filtered_mm = filtered_mm;
+    h->in_depth_metric = depth_metric;
+    h->in_color = color;
     return SF_OK;
 }
 static int check_full(sf_handle *h, int full_rows, int full_cols, int res) {
@@ -38,11 +47,8 @@ int sf_load_frame(sf_handle *h, int stream, const uint8_t *color_full, const uin
     HIP_TRY(hipSetDevice(h->device));
     if (int e = input_alloc(h)) return e;
     const size_t px = (size_t)full_rows * full_cols;
-    if (h->stage_px < px) {
-        if (int e = dev_alloc(h, &h->stage_color, px * 3)) return e;
-        if (int e = dev_alloc(h, &h->stage_depth, px)) return e;
-        h->stage_px = px;
-    }
+    if (int e = dev_grow(h, &h->stage_color, &h->stage_color_cap, px * 3)) return e;
+    if (int e = dev_grow(h, &h->stage_depth, &h->stage_depth_cap, px)) return e;
     HIP_TRY(hipMemcpyAsync(h->stage_color, color_full, px * 3, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->stage_depth, depth_full, px * 2, hipMemcpyHostToDevice, h->stream));
     if (int e = launch_load(h, h->stage_color, h->stage_depth, full_rows, full_cols, res_factor, stream, 1)) return e;

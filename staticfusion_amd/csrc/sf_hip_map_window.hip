@@ -55,10 +55,7 @@ static void launch_write(sf_handle *h, const WindowArgs *tab, int n, int max_cou
 static int partition(sf_handle *h, int n, sf_map *const *maps, const sfw_filter *filters, bool write, bool move_rest, int *selected,
                      const WindowArgs **d_tab, int *max_count_out) {
     HIP_TRY(hipSetDevice(h->device));
-    if (h->res_maps < (size_t)n) {
-        if (int e = dev_alloc(h, &h->res_dev, (size_t)n * 8)) return e;
-        h->res_maps = (size_t)n;
-    }
+    if (int e = results_scratch(h, (size_t)n)) return e;
     std::vector<WindowArgs> tab((size_t)n);
     int max_count = 0;
     for (int q = 0; q < n; q++) {

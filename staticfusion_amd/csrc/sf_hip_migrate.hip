@@ -9,14 +9,6 @@
 
 extern "C" {
 
-void migrate_release(sf_handle *h) {  // (the device blocks are in h->allocs)
-    for (auto &p : h->mig_tab_host)
-        if (p) (void)hipHostFree(p);
-    for (auto &e : h->mig_done)
-        if (e) (void)hipEventDestroy(e);
-    if (h->mig_ev) (void)hipEventDestroy(h->mig_ev);
-}
-
 int sfm_version(void) { return SFM_VERSION; }
 
 size_t sfm_blob_bytes(int rows, int cols, int levels, int with_input) {
@@ -52,31 +44,13 @@ static int layout_of(const sf_handle *h, int with_input, SfmLayout *lay) {
     return SF_OK;
 }
 
-// The table of one call goes to the device through the next slot of the handle's ring (pinned host block + device block) on
-// HIP stream `st`, without a host synchronisation: a slot is waited for only when the call four calls ago has not executed yet.
-// The caller launches its kernel on `st` and then calls table_done.
-static int table_upload(sf_handle *h, hipStream_t st, const void *entries, size_t bytes, void **dev, unsigned *slot_out) {
+// The table of one call goes to the device through the next slot of the handle's ring (SfRing, sf_resources.h) on HIP stream
+// `st`, without a host synchronisation: a slot is waited for only when the call four calls ago has not executed yet.
+// The caller launches its kernel on `st` and then calls h->mig_ring.done(st).
+static int table_upload(sf_handle *h, hipStream_t st, const void *entries, size_t bytes, void **dev) {
     const size_t cap = (size_t)h->k.batch * SFM_SEG_COUNT * SFM_ENTRY_BYTES;  // no call names more than every stream once
     if (bytes > cap) return fail(SF_ERR_ARG, "segment table larger than the handle");
-    const unsigned slot = h->mig_calls % sf_handle::MIG_SLOTS;
-    if (!h->mig_tab_dev[slot]) {
-        uint8_t *d = nullptr;
-        if (int e = dev_alloc(h, &d, cap)) return e;
-        h->mig_tab_dev[slot] = d;
-    }
-    if (!h->mig_tab_host[slot]) HIP_TRY(hipHostMalloc(&h->mig_tab_host[slot], cap, hipHostMallocDefault));
-    if (!h->mig_done[slot]) HIP_TRY(hipEventCreateWithFlags(&h->mig_done[slot], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(h->mig_done[slot]));
-    h->mig_calls++;
-    std::memcpy(h->mig_tab_host[slot], entries, bytes);
-    HIP_TRY(hipMemcpyAsync(h->mig_tab_dev[slot], h->mig_tab_host[slot], bytes, hipMemcpyHostToDevice, st));
-    *dev = h->mig_tab_dev[slot];
-    *slot_out = slot;
-    return SF_OK;
-}
-static int table_done(sf_handle *h, hipStream_t st, unsigned slot) {
-    HIP_TRY(hipEventRecord(h->mig_done[slot], st));
-    return SF_OK;
+    return h->mig_ring.next(h->own, cap, st, entries, bytes, dev);
 }
 
 static dim3 pair_grid(size_t pairs, size_t max_bytes) {
@@ -89,13 +63,12 @@ static dim3 pair_grid(size_t pairs, size_t max_bytes) {
 
 static int launch_copy(sf_handle *owner, hipStream_t st, const std::vector<SfmSeg> &segs) {
     void *dev = nullptr;
-    unsigned slot = 0;
-    if (int e = table_upload(owner, st, segs.data(), segs.size() * sizeof(SfmSeg), &dev, &slot)) return e;
+    if (int e = table_upload(owner, st, segs.data(), segs.size() * sizeof(SfmSeg), &dev)) return e;
     size_t max_bytes = 0;
     for (const SfmSeg &s : segs) max_bytes = std::max<size_t>(max_bytes, s.kind == SFM_KIND_BYTES ? s.bytes : 0);
     hipLaunchKernelGGL(sfm_copy_kernel, pair_grid(segs.size(), max_bytes), dim3(SFM_THREADS), 0, st, (const SfmSeg *)dev, (int)segs.size());
     HIP_TRY(hipGetLastError());
-    return table_done(owner, st, slot);
+    return owner->mig_ring.done(st);
 }
 
 static int check_list(const sf_handle *h, const int *streams, int n, bool distinct, const char *what) {
@@ -148,8 +121,9 @@ int sfm_copy_streams(sf_handle *dst, const int *dst_streams, int dst_im_count, s
     // after everything queued on both handles, before everything queued later on either: an event each way, no host wait
     const bool two = src->stream != dst->stream;
     if (two) {
-        if (!src->mig_ev) HIP_TRY(hipEventCreateWithFlags(&src->mig_ev, hipEventDisableTiming));
-        if (!dst->mig_ev) HIP_TRY(hipEventCreateWithFlags(&dst->mig_ev, hipEventDisableTiming));
+        for (sf_handle *q : {src, dst})
+            if (!q->mig_ev)
+                if (int e = q->own.event(&q->mig_ev, hipEventDisableTiming)) return e;
         HIP_TRY(hipEventRecord(src->mig_ev, src->stream));
         HIP_TRY(hipStreamWaitEvent(dst->stream, src->mig_ev, 0));
     }
@@ -163,10 +137,7 @@ int sfm_copy_streams(sf_handle *dst, const int *dst_streams, int dst_im_count, s
 }
 
 static int stage_for(sf_handle *h, size_t bytes) {
-    size_t cap = h->mig_stage_bytes;
-    if (int e = dev_grow(h, &h->mig_stage, &cap, bytes)) return e;
-    h->mig_stage_bytes = cap;
-    return SF_OK;
+    return dev_grow(h, &h->mig_stage, &h->mig_stage_bytes, bytes);
 }
 
 int sfm_export_stream(sf_handle *h, int stream, int im_count, void *blob, size_t blob_bytes) {
@@ -265,11 +236,10 @@ int sfm_reset_streams(sf_handle *h, const int *streams, int n) {
             if (f.kind == SFM_KIND_FILL) max_bytes = std::max<size_t>(max_bytes, f.bytes);
         }
     void *dev = nullptr;
-    unsigned slot = 0;
-    if (int e = table_upload(h, h->stream, fills.data(), fills.size() * sizeof(SfmFill), &dev, &slot)) return e;
+    if (int e = table_upload(h, h->stream, fills.data(), fills.size() * sizeof(SfmFill), &dev)) return e;
     hipLaunchKernelGGL(sfm_reset_kernel, pair_grid(fills.size(), max_bytes), dim3(SFM_THREADS), 0, h->stream, (const SfmFill *)dev, (int)fills.size());
     HIP_TRY(hipGetLastError());
-    return table_done(h, h->stream, slot);
+    return h->mig_ring.done(h->stream);
 }
 
 }  // extern "C"

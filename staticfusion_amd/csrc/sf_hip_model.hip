@@ -70,29 +70,18 @@ int check_map(const char *what, const sf_handle *h, const sf_map *m) {  // (shar
 }
 // device table for a batched launch: grows on demand, filled from a host copy that lives in the handle (shared: sf_host.h)
 int upload_table(sf_handle *h, const void *src, size_t bytes, void **dev) {
-    if (h->tab_bytes < bytes) {
-        unsigned char *q = nullptr;
-        if (int e = dev_alloc(h, &q, bytes * 2)) return e;  // the old block is freed with the handle
-        h->tab_dev = q;
-        h->tab_bytes = bytes * 2;
-    }
+    if (int e = dev_grow(h, &h->tab_dev, &h->tab_bytes, bytes)) return e;
     h->tab_host.assign((const unsigned char *)src, (const unsigned char *)src + bytes);
     HIP_TRY(hipMemcpyAsync(h->tab_dev, h->tab_host.data(), bytes, hipMemcpyHostToDevice, h->stream));
     *dev = h->tab_dev;
     return SF_OK;
 }
 static int predict_scratch(sf_handle *h, size_t n_maps) {
-    if (h->pr_maps >= n_maps) return SF_OK;
-    if (int e = dev_alloc(h, &h->pr_keys, n_maps * 2 * h->k.n0)) return e;
-    if (int e = dev_alloc(h, &h->pr_dense, n_maps * 2)) return e;
-    h->pr_maps = n_maps;
-    return SF_OK;
+    if (int e = dev_grow(h, &h->pr_keys, &h->pr_keys_cap, n_maps * 2 * h->k.n0)) return e;
+    return dev_grow(h, &h->pr_dense, &h->pr_dense_cap, n_maps * 2);
 }
-static int results_scratch(sf_handle *h, size_t n_maps) {
-    if (h->res_maps >= n_maps) return SF_OK;
-    if (int e = dev_alloc(h, &h->res_dev, n_maps * 8)) return e;
-    h->res_maps = n_maps;
-    return SF_OK;
+int results_scratch(sf_handle *h, size_t n_maps) {  // (shared: sf_host.h)
+    return dev_grow(h, &h->res_dev, &h->res_ints, n_maps * 8);
 }
 struct PredictJob {
     int stream;
@@ -248,15 +237,6 @@ int sf_get_prediction(sf_handle *h, int stream, float *depth, float *intensity) 
 }
 
 // ---- the surfel map (sf_fusion.h; struct sf_map: sf_host.h) ------------------------------------------
-static int map_alloc_bytes(sf_map *m, void **p, size_t bytes) {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    m->allocs.push_back(q);
-    *p = q;
-    return SF_OK;
-}
-#define map_alloc(m, p, count) map_alloc_bytes(m, (void **)(p), (size_t)(count) * sizeof(**(p)))
 int sf_map_create(sf_handle *h, int capacity, sf_map **out) {
     if (!h || !out || capacity < 0) return fail(SF_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -267,18 +247,18 @@ int sf_map_create(sf_handle *h, int capacity, sf_map **out) {
     m->h = h;
     m->capacity = (int)cap;
     const size_t n_cand_max = (size_t)((h->k.rows + 1) / 2) * ((h->k.cols + 1) / 2);
-    int e = SF_OK;
-    if (!e) e = map_alloc(m, &m->buf[0], cap * 12);
-    if (!e) e = map_alloc(m, &m->buf[1], cap * 12);
-    if (!e) e = map_alloc(m, &m->keys, n0 * 16);
+    int e = SF_OK;  // (the map's blocks are its own and not zero-filled)
+    if (!e) e = m->own.device(&m->buf[0], cap * 12, false);
+    if (!e) e = m->own.device(&m->buf[1], cap * 12, false);
+    if (!e) e = m->own.device(&m->keys, n0 * 16, false);
     if (!e && hipMemset(m->keys, 0xff, n0 * 16 * sizeof(unsigned long long)) != hipSuccess) e = fail(SF_ERR_DEVICE, "hipMemset");
-    if (!e) e = map_alloc(m, &m->occ, (size_t)h->k.cols * 4 * ((h->k.rows * 4 + 63) / 64));
-    if (!e) e = map_alloc(m, &m->index_export, n0 * 16);
-    if (!e) e = map_alloc(m, &m->winner, cap);
-    if (!e) e = map_alloc(m, &m->rec, n_cand_max * 12);
-    if (!e) e = map_alloc(m, &m->meta, n_cand_max * 2);
-    if (!e) e = map_alloc(m, &m->flags, cap + n_cand_max);
-    if (!e) e = map_alloc(m, &m->block_counts, (cap + n_cand_max + SF_CLEAN_BLOCK - 1) / SF_CLEAN_BLOCK + 1);
+    if (!e) e = m->own.device(&m->occ, (size_t)h->k.cols * 4 * ((h->k.rows * 4 + 63) / 64), false);
+    if (!e) e = m->own.device(&m->index_export, n0 * 16, false);
+    if (!e) e = m->own.device(&m->winner, cap, false);
+    if (!e) e = m->own.device(&m->rec, n_cand_max * 12, false);
+    if (!e) e = m->own.device(&m->meta, n_cand_max * 2, false);
+    if (!e) e = m->own.device(&m->flags, cap + n_cand_max, false);
+    if (!e) e = m->own.device(&m->block_counts, (cap + n_cand_max + SF_CLEAN_BLOCK - 1) / SF_CLEAN_BLOCK + 1, false);
     if (e) {
         sf_map_destroy(m);
         return e;
@@ -287,13 +267,10 @@ int sf_map_create(sf_handle *h, int capacity, sf_map **out) {
     *out = m;
     return SF_OK;
 }
-static void map_release(sf_map *m) {  // device memory of a map (its handle's device is current, its stream drained)
-    for (void *q : m->allocs) (void)hipFree(q);
-    m->allocs.clear();
-}
+// (a map's device memory is released with its handle's device current and its stream drained)
 void orphan_maps(sf_handle *h) {
     for (sf_map *m : h->maps) {
-        map_release(m);
+        m->own.release_all();
         m->h = nullptr;
     }
     h->maps.clear();
@@ -308,11 +285,11 @@ void sf_map_destroy(sf_map *m) {
                 h->maps.erase(it);
                 break;
             }
-        map_release(m);
+        m->own.release_all();
     }  // else: sf_destroy of the handle already released the memory and left the map as an empty shell
     delete m;
 }
-// include/sf_migrate.h: the map follows its stream to another handle. Its memory is its own (map_alloc) and stays where it is;
+// include/sf_migrate.h: the map follows its stream to another handle. Its memory is its own (sf_map::own) and stays where it is;
 // what changes is whose stream orders the work on it and whose sf_destroy releases it.
 int sfm_map_rebind(sf_map *m, sf_handle *dst) {
     if (!m || !dst) return fail(SF_ERR_ARG, "sfm_map_rebind: null");

@@ -68,26 +68,13 @@ int sf_advance_sequences_device(sf_handle *h, const void *pool_depth, const void
     for (size_t b = 0; b < B; b++)
         if (frame_index[b] >= pool_frames) return fail(SF_ERR_ARG, "frame_index entry outside the pool");
     HIP_TRY(hipSetDevice(h->device));
-    if (!h->seq_ready) {  // all or nothing: a failure leaves nothing half-initialised behind (the next call starts over)
-        if (!h->seq_index)
-            if (int e = dev_alloc(h, &h->seq_index, B * sf_handle::SEQ_SLOTS)) return e;
-        if (!h->seq_index_host) HIP_TRY(hipHostMalloc((void **)&h->seq_index_host, sizeof(int) * B * sf_handle::SEQ_SLOTS, hipHostMallocDefault));
-        for (auto &e : h->seq_done)
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->seq_ready = true;
-    }
-    const unsigned slot = h->seq_calls % sf_handle::SEQ_SLOTS;
-    if (h->seq_calls >= (unsigned)sf_handle::SEQ_SLOTS) HIP_TRY(hipEventSynchronize(h->seq_done[slot]));  // eight calls ago
-    h->seq_calls++;
-    int *host = h->seq_index_host + slot * B, *dev = h->seq_index + slot * B;
-    std::memcpy(host, frame_index, sizeof(int) * B);
-    HIP_TRY(hipMemcpyAsync(dev, host, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    void *dev = nullptr;
+    if (int e = h->seq_ring.next(h->own, sizeof(int) * B, h->stream, frame_index, sizeof(int) * B, &dev)) return e;
     const dim3 grid((unsigned)std::min(16, (h->k.n0 / 4 + 255) / 256), (unsigned)h->k.batch);
     hipLaunchKernelGGL(sf_advance_kernel, grid, dim3(256), 0, h->stream, h->k.pyr_new[0], h->k.pyr_new[1], h->k.pyr_pred[0], h->k.pyr_pred[1],
                        (const float *)pool_depth, (const float *)pool_intensity, (const int *)dev, h->k.n0, h->k.n_tot);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->seq_done[slot], h->stream));
-    return SF_OK;
+    return h->seq_ring.done(h->stream);
 }
 
 // ---- overlapped upload: the next batch of frames crosses PCIe on a second HIP stream while the solver runs ----
@@ -96,12 +83,22 @@ int sf_upload_current_async(sf_handle *h, const float *depth_batch, const float 
     if (h->upload_pending) return fail(SF_ERR_STATE, "an upload is already pending: call sf_commit_upload first");
     HIP_TRY(hipSetDevice(h->device));
     const size_t n = (size_t)h->k.n0 * h->k.batch;
-    if (!h->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&h->copy_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&h->compute_done, hipEventDisableTiming));
-        if (int e = dev_alloc(h, &h->up_depth, n)) return e;
-        if (int e = dev_alloc(h, &h->up_inten, n)) return e;
+    if (!h->copy_stream) {  // a group (sf_resources.h): the five exist together or not at all
+        SfOwner g;
+        hipStream_t st = nullptr;
+        hipEvent_t copy_done = nullptr, compute_done = nullptr;
+        float *depth = nullptr, *inten = nullptr;
+        if (int e = g.stream(&st, hipStreamNonBlocking)) return e;
+        if (int e = g.event(&copy_done, hipEventDisableTiming)) return e;
+        if (int e = g.event(&compute_done, hipEventDisableTiming)) return e;
+        if (int e = g.device(&depth, n)) return e;
+        if (int e = g.device(&inten, n)) return e;
+        h->own.adopt(g);
+        h->copy_stream = st;
+        h->copy_done = copy_done;
+        h->compute_done = compute_done;
+        h->up_depth = depth;
+        h->up_inten = inten;
     }
     // the staging block may still be read by the previous commit's copy on the compute stream
     HIP_TRY(hipStreamWaitEvent(h->copy_stream, h->compute_done, 0));
@@ -204,23 +201,13 @@ static int multi_buffers(sf_handle *h, int n_frames, bool want_index, bool want_
         if (int e = dev_alloc(h, &h->d_frame_done, B)) return e;
     // Each buffer only when this call needs it, each with its own capacity (at 16 384 streams and 4096 frames the three
     // together would be 4.3 GB of HBM + 268 MB of pinned memory; sf_process_frames without T_out needs none of them).
-    // Growing: the old block may still be in use by a queued launch.
-    if (want_index && n_frames > h->multi_capacity) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_multi_index) (void)hipFree(h->d_multi_index);
-        if (h->h_multi_index) (void)hipHostFree(h->h_multi_index);
-        h->d_multi_index = nullptr; h->h_multi_index = nullptr; h->multi_capacity = 0;
-        HIP_TRY(hipMalloc((void **)&h->d_multi_index, sizeof(int) * B * n_frames));
-        HIP_TRY(hipHostMalloc((void **)&h->h_multi_index, sizeof(int) * B * n_frames, hipHostMallocDefault));
-        h->multi_capacity = n_frames;
+    // Growing (dev_grow): the old block may still be in use by a queued launch. Every call fills what it reads: no zero-fill.
+    if (want_index) {
+        if (int e = h->own.grow(&h->d_multi_index, &h->d_multi_cap, B * n_frames, h->stream, false)) return e;
+        if (int e = h->own.grow_pinned(&h->h_multi_index, &h->h_multi_cap, B * n_frames, h->stream)) return e;
     }
-    if (want_traj && n_frames > h->traj_capacity) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_traj) (void)hipFree(h->d_traj);
-        h->d_traj = nullptr; h->traj_capacity = 0;
-        HIP_TRY(hipMalloc((void **)&h->d_traj, sizeof(float) * 16 * B * n_frames));
-        h->traj_capacity = n_frames;
-    }
+    if (want_traj)
+        if (int e = h->own.grow(&h->d_traj, &h->traj_cap, 16 * B * n_frames, h->stream, false)) return e;
     return SF_OK;
 }
 static int process_frames(sf_handle *h, const void *pool_depth, const void *pool_intensity, const int32_t *frame_index, int pool_frames,
@@ -399,8 +386,9 @@ int sf_get_jacobian_rows(sf_handle *h, int stream, float *A, float *B, int *n_ro
     const int L = st.last_level;
     if (L < 0 || L >= h->k.levels || st.cum_frames == 0) return fail(SF_ERR_STATE, "no outer iteration executed yet");
     const size_t n = h->k.ln[L];
+    SfOwner call;  // the 14 planes of this call, released on every return path
     float *dev = nullptr;
-    HIP_TRY(hipMalloc((void **)&dev, 14 * n * sizeof(float)));
+    if (int e = call.device(&dev, 14 * n, false)) return e;
     std::vector<float> planes(14 * n);
     if (h->args_dirty) {
         HIP_TRY(hipMemcpyAsync(h->d_args, &h->k, sizeof(KArgs), hipMemcpyHostToDevice, h->stream));
@@ -410,7 +398,6 @@ int sf_get_jacobian_rows(sf_handle *h, int stream, float *A, float *B, int *n_ro
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(planes.data(), dev, planes.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(dev);
     if (e != hipSuccess) return fail(SF_ERR_DEVICE, std::string("sf_get_jacobian_rows: ") + hipGetErrorString(e));
     int rows = 0;  // validPixels order of the reference = ascending column-major index (u outer, v inner)
     for (size_t q = 0; q < n; q++) {
@@ -559,43 +546,30 @@ int sf_microbench_pass(sf_handle *h, int which, int variant, int reps, float *el
 int sf_microbench_copy(sf_handle *h, size_t bytes, int reps, float *elapsed_ms) {
     if (!h || !elapsed_ms || bytes < 4096 || (bytes & 15u) || bytes > ((size_t)1 << 36) || reps < 1 || reps > 1000) return fail(SF_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    void *src = nullptr, *dst = nullptr;
-    if (hipMalloc(&src, bytes) != hipSuccess || hipMalloc(&dst, bytes) != hipSuccess) {
+    SfOwner call;  // two blocks and two events of this call, released on every return path
+    unsigned char *src = nullptr, *dst = nullptr;
+    if (call.device(&src, bytes, false) || call.device(&dst, bytes, false)) {
         (void)hipGetLastError();
-        if (src) (void)hipFree(src);
         return fail(SF_ERR_NOMEM, "sf_microbench_copy: scratch blocks");
     }
-    int e = SF_OK;
     float ms = 0.f;
     // events of its own: the handle's ev0 / ev1 belong to the timed_* entry points, evk0 / evk1 to the solver launches
     // (sf_last_solver_kernel_ms goes on reporting the last of those)
     hipEvent_t c0 = nullptr, c1 = nullptr;
-    if (hipEventCreate(&c0) != hipSuccess || hipEventCreate(&c1) != hipSuccess) {
+    if (call.event(&c0, hipEventDefault) || call.event(&c1, hipEventDefault)) {
         (void)hipGetLastError();
-        if (c0) (void)hipEventDestroy(c0);
-        (void)hipFree(src);
-        (void)hipFree(dst);
         return fail(SF_ERR_DEVICE, "sf_microbench_copy: events");
     }
     const size_t n16 = bytes / 16;
     const int grid = (int)std::min<size_t>((n16 + 255) / 256, (size_t)std::max(1, h->max_blocks / std::max(1, h->wg_per_cu)) * 8);
-    auto body = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(src, 0x3c, bytes, h->stream));
-        hipLaunchKernelGGL(sf_copy_kernel, dim3(grid), dim3(256), 0, h->stream, (const float4 *)src, (float4 *)dst, n16);  // warm-up: page tables, clocks
-        HIP_TRY(hipEventRecord(c0, h->stream));
-        for (int r = 0; r < reps; r++) hipLaunchKernelGGL(sf_copy_kernel, dim3(grid), dim3(256), 0, h->stream, (const float4 *)src, (float4 *)dst, n16);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c1, h->stream));
-        HIP_TRY(hipEventSynchronize(c1));
-        HIP_TRY(hipEventElapsedTime(&ms, c0, c1));
-        return SF_OK;
-    };
-    e = body();
-    (void)hipEventDestroy(c0);
-    (void)hipEventDestroy(c1);
-    (void)hipFree(src);
-    (void)hipFree(dst);
-    if (e) return e;
+    HIP_TRY(hipMemsetAsync(src, 0x3c, bytes, h->stream));
+    hipLaunchKernelGGL(sf_copy_kernel, dim3(grid), dim3(256), 0, h->stream, (const float4 *)src, (float4 *)dst, n16);  // warm-up: page tables, clocks
+    HIP_TRY(hipEventRecord(c0, h->stream));
+    for (int r = 0; r < reps; r++) hipLaunchKernelGGL(sf_copy_kernel, dim3(grid), dim3(256), 0, h->stream, (const float4 *)src, (float4 *)dst, n16);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c1, h->stream));
+    HIP_TRY(hipEventSynchronize(c1));
+    HIP_TRY(hipEventElapsedTime(&ms, c0, c1));
     *elapsed_ms = ms;
     return SF_OK;
 }

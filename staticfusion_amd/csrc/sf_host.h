@@ -1,5 +1,7 @@
 // sf_host.h — what the host-side translation units of libsf_hip.so share: the handle, the error helpers, device
 // allocation, and the few functions one part calls in another. Nothing here is exported (include/sf.h is the ABI).
+//   sf_resources.h     the owner of every device block, pinned block, event and stream (SfOwner), the one growth rule
+//                      (SfOwner::grow, here dev_grow) and the ring of per-call tables (SfRing); host only, no kernel
 //   sf_hip.hip         handle lifetime, parameters, the builds of the frame kernel, launch()
 //   sf_hip_solver.hip  images in, frames (one or several per launch), results and debug planes out, measurement support
 //   sf_hip_input.hip   the input stage: loader decimation / RGB -> intensity, bilateral depth filter (sf_input.h)
@@ -26,8 +28,7 @@
 
 #include "sf_cluster.h"
 #include "sf_device_common.h"
-
-#define SF_INTERNAL __attribute__((visibility("hidden")))
+#include "sf_resources.h"  // SF_INTERNAL, sf_fail, SfOwner, SfRing
 
 // the two builds of the frame kernels (sf_frame_kernels.hip, -DSF_NT=256 / -DSF_NT=1024)
 struct FrameVariant {
@@ -56,7 +57,7 @@ struct sf_handle {
     bool solver_timed = false;
     KArgs *d_args = nullptr;  // device copy of k (geometry, parameters, buffer table)
     bool args_dirty = true;
-    std::vector<void *> allocs;
+    SfOwner own;  // every device block, pinned block, event and stream of the handle (sf_resources.h): sf_destroy releases it
     // input stage (sf_input.h), allocated by the first sf_load_frame*
     float depth_cutoff = 4.5f;  // FrontEnd.cpp:168
     bool have_frame = false;
@@ -65,11 +66,11 @@ struct sf_handle {
     uint8_t *in_color = nullptr;
     uint8_t *stage_color = nullptr;  // one full-resolution frame, for the host-pointer variant
     uint16_t *stage_depth = nullptr;
-    size_t stage_px = 0;
+    size_t stage_color_cap = 0, stage_depth_cap = 0;  // capacities in elements (dev_grow)
     // model prediction (sf_predict.h), allocated by the first sf_predict_from_model
     unsigned long long *pr_keys = nullptr;  // per batched map: low and high key image (2 x n0)
     int *pr_dense = nullptr;                // per batched map: 2 ints (density sum; init-model counts)
-    size_t pr_maps = 0;                     // how many maps the two blocks above are sized for
+    size_t pr_keys_cap = 0, pr_dense_cap = 0;  // capacities of the two blocks above in elements (dev_grow)
     bool pr_rendered = false;
     std::vector<int> pr_job_of_stream;      // per stream: index of the job of the last predict batch that rendered into it, or -1
     vfloat4 *pr_rays = nullptr;             // view ray per pixel for the intrinsics below (sf_predict_rays_kernel)
@@ -77,45 +78,37 @@ struct sf_handle {
     float *pr_surfels = nullptr;
     size_t pr_floats = 0;                   // capacity of pr_surfels in floats (12 per surfel)
     // argument tables of the batched map kernels (sf_predict.h, sf_fusion.h): device block + the host copy it is filled from
-    void *tab_dev = nullptr;
+    unsigned char *tab_dev = nullptr;
     size_t tab_bytes = 0;
     std::vector<unsigned char> tab_host;
     int *res_dev = nullptr;                 // per batched map: 8 ints of results
-    size_t res_maps = 0;
+    size_t res_ints = 0;                    // capacity of res_dev in ints
     // overlapped host -> HBM upload of the next frames (sf_upload_current_async): copy stream, staging, event
     hipStream_t copy_stream = nullptr;
     hipEvent_t copy_done = nullptr, compute_done = nullptr;
     float *up_depth = nullptr, *up_inten = nullptr;
     bool upload_pending = false;
     // sf_advance_sequences_device: per-stream frame numbers, a ring of device + pinned host slots so that calls queue up
-    // behind running frame kernels without a host synchronisation (a slot is reused only after its copy has executed)
-    static const int SEQ_SLOTS = 8;
-    int *seq_index = nullptr;
-    int *seq_index_host = nullptr;
-    hipEvent_t seq_done[SEQ_SLOTS] = {};
-    unsigned seq_calls = 0;
-    bool seq_ready = false;  // index ring + events all created
+    // behind running frame kernels without a host synchronisation (a slot is reused only after its copy has executed).
+    // All eight slots are made by the first call: no later call allocates.
+    SfRing<8, true> seq_ring;
     // multi-frame launches (sf_process_frames / sf_process_sequence_frames_device)
     int *d_frame_done = nullptr;     // [batch]
-    int *d_multi_index = nullptr;    // [capacity frames][batch]
+    int *d_multi_index = nullptr;    // [frames][batch]
     int *h_multi_index = nullptr;    // pinned staging of the same size
-    float *d_traj = nullptr;         // [capacity frames][batch][16]
-    int multi_capacity = 0;          // frames the two index buffers hold
-    int traj_capacity = 0;           // frames d_traj holds
+    float *d_traj = nullptr;         // [frames][batch][16]
+    size_t d_multi_cap = 0, h_multi_cap = 0, traj_cap = 0;  // capacities of the three in elements (dev_grow)
     int solver_timed_frames = 1;     // frames of the launch evk0 / evk1 bracket
     // stream migration (sf_hip_migrate.hip): the per-call segment tables, a ring of device + pinned host slots like the one of
-    // sf_advance_sequences_device (a call queues up behind running kernels; a slot is reused after its kernel has executed),
-    // the event the two handles of a copy order their HIP streams with, and the staging block of export / import
-    static const int MIG_SLOTS = 4;
-    void *mig_tab_dev[MIG_SLOTS] = {};
-    void *mig_tab_host[MIG_SLOTS] = {};
-    hipEvent_t mig_done[MIG_SLOTS] = {};
-    unsigned mig_calls = 0;
+    // sf_advance_sequences_device (a call queues up behind running kernels; a slot is reused after its kernel has executed)
+    // whose slots are made one by one as calls first reach them, the event the two handles of a copy order their HIP streams
+    // with, and the staging block of export / import
+    SfRing<4, false> mig_ring;
     hipEvent_t mig_ev = nullptr;
     uint8_t *mig_stage = nullptr;
     size_t mig_stage_bytes = 0;
     // free-view rendering (sf_hip_view.hip): one block for the key images, ray tables, large-sprite lists, argument tables and
-    // output staging of a call, grown when a call needs more (dev_grow: in h->allocs, freed with the handle); the host copy
+    // output staging of a call, grown when a call needs more (dev_grow); the host copy
     // the tables are filled from; where the per-view list counters of the last call lie in the block
     unsigned char *view_scratch = nullptr;
     size_t view_bytes = 0;
@@ -144,7 +137,7 @@ struct sf_map {
     int *block_counts = nullptr;
     bool have_index = false;
     int epoch = 0;  // index images rendered since the key image was last filled with ones; tag = 255 - epoch
-    std::vector<void *> allocs;
+    SfOwner own;    // the map's device blocks (not zero-filled): released by sf_map_destroy, or by its handle's sf_destroy
 };
 
 // Constructor state of a stream (reference FrontEnd.cpp:79-81,110,152-154), as the 32-bit word at byte offset `off` of its
@@ -168,9 +161,7 @@ __host__ __device__ static inline uint32_t sf_ctor_state_word(size_t off, float 
     return 0u;
 }
 
-// the thread's last error text (sf_last_error); returns `code`
-SF_INTERNAL int sf_fail(int code, const std::string &msg);
-#define fail sf_fail
+#define fail sf_fail  // (sf_resources.h)
 #define HIP_TRY(expr)                                                                                  \
     do {                                                                                               \
         hipError_t e_ = (expr);                                                                        \
@@ -178,41 +169,14 @@ SF_INTERNAL int sf_fail(int code, const std::string &msg);
             return fail(SF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));             \
     } while (0)
 
+// a zero-filled device block of the handle, and the growth rule on the handle's stream (SfOwner: sf_resources.h)
 template <class T>
 static int dev_alloc(sf_handle *h, T **p, size_t count) {
-    void *q = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    e = hipMemset(q, 0, bytes);
-    if (e != hipSuccess) return fail(SF_ERR_DEVICE, std::string("hipMemset: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (T *)q;
-    return SF_OK;
+    return h->own.device(p, count);
 }
-
-// Grow a device block of the handle to at least `count` elements: geometric growth (a map that gains a few surfels every
-// frame must not allocate every frame) and the old block is released -- after the stream has drained, nothing queued still
-// reads it -- instead of living on until sf_destroy.
 template <class T>
 static int dev_grow(sf_handle *h, T **p, size_t *capacity, size_t count) {
-    if (*capacity >= count) return SF_OK;
-    const size_t want = std::max(count, *capacity + *capacity / 2 + 1024);
-    T *old = *p;
-    T *fresh = nullptr;
-    if (int e = dev_alloc(h, &fresh, want)) return e;
-    if (old) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-            if (*it == (void *)old) {
-                h->allocs.erase(it);
-                break;
-            }
-        HIP_TRY(hipFree(old));
-    }
-    *p = fresh;
-    *capacity = want;
-    return SF_OK;
+    return h->own.grow(p, capacity, count, h->stream);
 }
 
 // shared between the parts (defined in the file named)
@@ -258,5 +222,5 @@ SF_INTERNAL void invert_pose(const float pose[16], float out[16]);            //
 SF_INTERNAL int check_map(const char *what, const sf_handle *h, const sf_map *m);
 // sf_hip_model.hip: the table of a batched launch into h->tab_dev (grown on demand; it stays there for later launches of the call)
 SF_INTERNAL int upload_table(sf_handle *h, const void *src, size_t bytes, void **dev);
-SF_INTERNAL void migrate_release(sf_handle *h);                               // sf_hip_migrate.hip: sf_destroy releases the pinned tables and events
+SF_INTERNAL int results_scratch(sf_handle *h, size_t n_maps);                 // sf_hip_model.hip: h->res_dev holds 8 ints per batched map
 }

@@ -1,0 +1,336 @@
+// The host-side resource owner (staticfusion_amd/csrc/sf_resources.h: SfOwner, its growth rule, SfRing) played through on the
+// CPU. Stand-alone: the HIP functions the header calls are defined HERE -- malloc-backed, with a set of live pointers (a free
+// of an unknown one aborts), a log of calls and "fail the k-th acquiring call" --, and so is sf_fail. No HIP runtime, no
+// library. tests/test_host_resources_cpu.py compiles it with -fsanitize=address,undefined and runs it as a child process: once
+// without a failure, then once for every acquiring call of that run failing. It prints "ok <runs>" and returns 0, or names
+// the first failure and returns 1. What is still allocated at exit is LeakSanitizer's to report.
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+
+#include "../../staticfusion_amd/csrc/sf_resources.h"
+
+// ---- the HIP runtime of this program ---------------------------------------------------------------------------------
+enum Op { MALLOC, FREE, HOST_MALLOC, HOST_FREE, EVENT_CREATE, EVENT_DESTROY, STREAM_CREATE, STREAM_DESTROY, STREAM_SYNC, EVENT_SYNC, EVENT_RECORD, MEMCPY, MEMSET };
+struct Call {
+    Op op;
+    const void *p;
+};
+static std::map<const void *, Op> live;  // pointer -> the call that made it
+static std::vector<Call> calls;
+static int acquired = 0;   // acquiring calls so far in this run
+static int fail_at = 0;    // the acquiring call that fails (1-based), 0: none
+static bool fired = false; // ... and it has
+static Op failed_op = MALLOC;  // ... and which kind it was
+static std::string last_error;
+
+int sf_fail(int code, const std::string &msg) {
+    last_error = msg;
+    return code;
+}
+
+static hipError_t acquire(Op op, void **out, size_t bytes) {
+    if (++acquired == fail_at) {
+        fired = true;
+        failed_op = op;
+        return op == MALLOC ? hipErrorOutOfMemory : hipErrorUnknown;
+    }
+    void *p = std::malloc(bytes ? bytes : 1);
+    if (!p) std::abort();
+    live[p] = op;
+    calls.push_back({op, p});
+    *out = p;
+    return hipSuccess;
+}
+static hipError_t release(Op op, Op made_by, void *p) {
+    const auto it = live.find(p);
+    if (it == live.end() || it->second != made_by) {
+        std::fprintf(stderr, "release (op %d) of a pointer that is not live or of another kind\n", (int)op);
+        std::abort();
+    }
+    live.erase(it);
+    calls.push_back({op, p});
+    std::free(p);
+    return hipSuccess;
+}
+static void must_be_live(const void *p, Op made_by) {
+    const auto it = live.find(p);
+    if (it == live.end() || it->second != made_by) {
+        std::fprintf(stderr, "use of a pointer that is not live\n");
+        std::abort();
+    }
+}
+extern "C" {
+hipError_t hipMalloc(void **p, size_t bytes) { return acquire(MALLOC, p, bytes); }
+hipError_t hipFree(void *p) { return release(FREE, MALLOC, p); }
+hipError_t hipHostMalloc(void **p, size_t bytes, unsigned) { return acquire(HOST_MALLOC, p, bytes); }
+hipError_t hipHostFree(void *p) { return release(HOST_FREE, HOST_MALLOC, p); }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return acquire(EVENT_CREATE, (void **)e, 1); }
+hipError_t hipEventDestroy(hipEvent_t e) { return release(EVENT_DESTROY, EVENT_CREATE, e); }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return acquire(STREAM_CREATE, (void **)s, 1); }
+hipError_t hipStreamDestroy(hipStream_t s) { return release(STREAM_DESTROY, STREAM_CREATE, s); }
+hipError_t hipMemset(void *p, int v, size_t bytes) {
+    must_be_live(p, MALLOC);
+    std::memset(p, v, bytes);
+    calls.push_back({MEMSET, p});
+    return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) {
+    must_be_live(s, STREAM_CREATE);
+    calls.push_back({STREAM_SYNC, s});
+    return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) {
+    must_be_live(e, EVENT_CREATE);
+    calls.push_back({EVENT_SYNC, e});
+    return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    must_be_live(e, EVENT_CREATE);
+    must_be_live(s, STREAM_CREATE);
+    calls.push_back({EVENT_RECORD, e});
+    return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t s) {
+    must_be_live(dst, MALLOC);
+    must_be_live(s, STREAM_CREATE);
+    std::memcpy(dst, src, bytes);
+    calls.push_back({MEMCPY, dst});
+    return hipSuccess;
+}
+const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "unknown error"; }
+}
+
+// ---- the scenario ---------------------------------------------------------------------------------------------------
+static long checks = 0;
+#define CHECK(cond)                                                                             \
+    do {                                                                                        \
+        checks++;                                                                               \
+        if (!(cond)) {                                                                          \
+            std::printf("FAILED %s:%d (failing call %d): %s\n", __FILE__, __LINE__, fail_at, #cond); \
+            return 1;                                                                           \
+        }                                                                                       \
+    } while (0)
+
+// a handle in miniature: the members the product's groups, grown blocks and rings set
+struct SF_INTERNAL Mini {  // (hidden like the types it holds)
+    SfOwner own;
+    hipStream_t stream = nullptr;
+    int *in0 = nullptr, *in1 = nullptr, *in2 = nullptr, *in3 = nullptr;  // like input_alloc
+    hipStream_t copy_stream = nullptr;                                  // like the set-up of sf_upload_current_async
+    hipEvent_t copy_done = nullptr, compute_done = nullptr;
+    float *up0 = nullptr, *up1 = nullptr;
+    float *block = nullptr;
+    size_t block_cap = 0;
+    int *pin = nullptr;
+    size_t pin_cap = 0;
+    SfRing<4, false> lazy;
+    SfRing<8, true> eager;
+};
+static int group_of_four(Mini &m) {
+    if (m.in0) return SF_OK;
+    SfOwner g;
+    int *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr;
+    if (int e = g.device(&a, 100)) return e;
+    if (int e = g.device(&b, 100)) return e;
+    if (int e = g.device(&c, 100)) return e;
+    if (int e = g.device(&d, 300)) return e;
+    m.own.adopt(g);
+    m.in0 = a; m.in1 = b; m.in2 = c; m.in3 = d;
+    return SF_OK;
+}
+static int group_of_upload(Mini &m) {
+    if (m.copy_stream) return SF_OK;
+    SfOwner g;
+    hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float *a = nullptr, *b = nullptr;
+    if (int e = g.stream(&st, hipStreamNonBlocking)) return e;
+    if (int e = g.event(&e0, hipEventDisableTiming)) return e;
+    if (int e = g.event(&e1, hipEventDisableTiming)) return e;
+    if (int e = g.device(&a, 64)) return e;
+    if (int e = g.device(&b, 64)) return e;
+    m.own.adopt(g);
+    m.copy_stream = st; m.copy_done = e0; m.compute_done = e1; m.up0 = a; m.up1 = b;
+    return SF_OK;
+}
+static int call_local(bool leave_early) {  // like sf_microbench_copy: everything goes with the call, on every path
+    SfOwner call;
+    char *a = nullptr, *b = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (int e = call.device(&a, 4096, false)) return e;
+    if (int e = call.device(&b, 4096, false)) return e;
+    if (int e = call.event(&e0, hipEventDefault)) return e;
+    if (leave_early) return SF_OK;
+    if (int e = call.event(&e1, hipEventDefault)) return e;
+    return SF_OK;
+}
+
+// One step. If the run's failing call fell into it: the documented code came back, `untouched` holds (what the step would
+// have set is as it was), and the same step once more, now without a failure, succeeds.
+template <class Step, class Untouched>
+static int step(Step run, Untouched untouched) {
+    const int before = acquired;
+    const bool had_fired = fired;
+    int r = run();
+    if (fired && !had_fired) {
+        // device memory: SF_ERR_NOMEM, "hipMalloc: <HIP's text>"; pinned memory, events, streams: SF_ERR_DEVICE and their call's name
+        if (failed_op == MALLOC) CHECK(r == SF_ERR_NOMEM && last_error == "hipMalloc: out of memory");
+        else CHECK(r == SF_ERR_DEVICE && last_error == std::string(failed_op == HOST_MALLOC ? "hipHostMalloc" : failed_op == EVENT_CREATE ? "hipEventCreate" : "hipStreamCreate") + ": unknown error");
+        CHECK(acquired > before);
+        CHECK(untouched());
+        r = run();
+    }
+    CHECK(r == SF_OK);
+    return 0;
+}
+static size_t count_op(size_t from, Op op, const void *p = nullptr) {
+    size_t n = 0;
+    for (size_t q = from; q < calls.size(); q++) n += calls[q].op == op && (!p || calls[q].p == p);
+    return n;
+}
+static long find_op(size_t from, Op op, const void *p) {
+    for (size_t q = from; q < calls.size(); q++)
+        if (calls[q].op == op && calls[q].p == p) return (long)q;
+    return -1;
+}
+template <class Ring>
+static bool ring_consistent(const Ring &r, int n) {
+    for (int q = 0; q < n; q++)
+        if (r.made(q) ? !(r.host[q] && r.dev[q] && r.event[q]) : (r.host[q] || r.dev[q] || r.event[q])) return false;
+    return true;
+}
+
+static int scenario(int failing, int *acquiring_calls) {
+    live.clear();
+    calls.clear();
+    acquired = 0;
+    fail_at = failing;
+    fired = false;
+    {
+        Mini m;
+        // the handle's stream: everything below drains or copies on it
+        if (step([&] { return m.stream ? SF_OK : m.own.stream(&m.stream, hipStreamDefault); }, [&] { return m.stream == nullptr && live.empty(); })) return 1;
+
+        // ---- a group of four blocks
+        size_t n_live = live.size();
+        if (step([&] { return group_of_four(m); }, [&] { return !m.in0 && !m.in1 && !m.in2 && !m.in3 && live.size() == n_live && m.own.dev.empty(); })) return 1;
+        CHECK(m.in0 && m.in1 && m.in2 && m.in3 && live.size() == n_live + 4 && m.own.dev.size() == 4);
+        for (int q = 0; q < 300; q++) CHECK(m.in3[q] == 0);  // zero-filled
+        CHECK(group_of_four(m) == SF_OK && live.size() == n_live + 4);  // made: nothing more
+
+        // ---- a group of a stream, two events and two blocks
+        n_live = live.size();
+        if (step([&] { return group_of_upload(m); },
+                 [&] { return !m.copy_stream && !m.copy_done && !m.compute_done && !m.up0 && !m.up1 && live.size() == n_live && m.own.streams.size() == 1; }))
+            return 1;
+        CHECK(m.copy_stream && m.copy_done && m.compute_done && m.up0 && m.up1 && live.size() == n_live + 5);
+
+        // ---- a block grown three times, one of them a no-op; then once past the geometric step
+        size_t mark = calls.size();
+        if (step([&] { return m.own.grow(&m.block, &m.block_cap, 2000, m.stream); }, [&] { return !m.block && m.block_cap == 0; })) return 1;
+        CHECK(m.block && m.block_cap == 2000);                   // the first request is exact
+        CHECK(count_op(mark, STREAM_SYNC) == 0 && count_op(mark, FREE) == 0);  // nothing outgrown: no drain
+        mark = calls.size();
+        float *const first = m.block;
+        CHECK(m.own.grow(&m.block, &m.block_cap, 1500, m.stream) == SF_OK);
+        CHECK(m.block == first && m.block_cap == 2000 && calls.size() == mark);  // a no-op makes no call at all
+        n_live = live.size();
+        if (step([&] { return m.own.grow(&m.block, &m.block_cap, 2001, m.stream); }, [&] { return m.block == first && m.block_cap == 2000 && live.size() == n_live; })) return 1;
+        CHECK(m.block != first && m.block_cap == 2000 + 1000 + 1024 && live.size() == n_live);
+        {
+            const long made = find_op(mark, MALLOC, m.block), drained = find_op(mark, STREAM_SYNC, m.stream), freed = find_op(mark, FREE, first);
+            CHECK(made >= 0 && made < drained && drained < freed);  // allocate new, drain, free old
+            CHECK(count_op(0, FREE, first) == 1);                    // ... exactly once
+        }
+        if (step([&] { return m.own.grow(&m.block, &m.block_cap, 10000, m.stream, false); }, [&] { return m.block_cap == 4024; })) return 1;
+        CHECK(m.block_cap == 10000);
+
+        // ---- a pinned block grown
+        if (step([&] { return m.own.grow_pinned(&m.pin, &m.pin_cap, 5000, m.stream); }, [&] { return !m.pin && m.pin_cap == 0; })) return 1;
+        int *const first_pin = m.pin;
+        CHECK(first_pin && m.pin_cap == 5000 && live.at(first_pin) == HOST_MALLOC);
+        mark = calls.size();
+        if (step([&] { return m.own.grow_pinned(&m.pin, &m.pin_cap, 5001, m.stream); }, [&] { return m.pin == first_pin && m.pin_cap == 5000; })) return 1;
+        CHECK(m.pin != first_pin && m.pin_cap == 5000 + 2500 + 1024);
+        {
+            const long drained = find_op(mark, STREAM_SYNC, m.stream), freed = find_op(mark, HOST_FREE, first_pin);
+            CHECK(drained >= 0 && drained < freed && count_op(0, HOST_FREE, first_pin) == 1);
+        }
+
+        // ---- a ring whose slots are made as they are reached, ten uploads
+        for (unsigned i = 0; i < 10; i++) {
+            const unsigned slot = i % 4;
+            const unsigned table[4] = {i, i * 3, i * 5, 0xabcdu};
+            void *dev = nullptr;
+            mark = calls.size();
+            n_live = live.size();
+            if (step([&] { return m.lazy.next(m.own, 64, m.stream, table, sizeof table, &dev); },
+                     [&] { return !m.lazy.made(slot) && m.lazy.calls == i && live.size() == n_live && ring_consistent(m.lazy, 4); }))
+                return 1;
+            CHECK(m.lazy.calls == i + 1 && dev == m.lazy.dev[slot] && ring_consistent(m.lazy, 4));
+            CHECK(std::memcmp(dev, table, sizeof table) == 0 && std::memcmp(m.lazy.host[slot], table, sizeof table) == 0);
+            CHECK(live.size() == n_live + (i < 4 ? 3 : 0));  // a slot is made by the call that first reaches it, and only then
+            for (unsigned q = 0; q < 4; q++) CHECK(m.lazy.made(q) == (q <= i));
+            // waited for before its reuse -- and before the copy into it --, not before its first use
+            const long waited = find_op(mark, EVENT_SYNC, m.lazy.event[slot]), copied = find_op(mark, MEMCPY, dev);
+            CHECK(count_op(mark, EVENT_SYNC) == (i >= 4 ? 1u : 0u) && copied >= 0 && (i < 4 || (waited >= 0 && waited < copied)));
+            mark = calls.size();
+            CHECK(m.lazy.done(m.stream) == SF_OK);
+            CHECK(calls.size() == mark + 1 && find_op(mark, EVENT_RECORD, m.lazy.event[slot]) == (long)mark);
+        }
+
+        // ---- a ring made at once, ten uploads
+        for (unsigned i = 0; i < 10; i++) {
+            const unsigned slot = i % 8;
+            const int frames[3] = {(int)i, -1, 7};
+            void *dev = nullptr;
+            mark = calls.size();
+            n_live = live.size();
+            if (step([&] { return m.eager.next(m.own, sizeof frames, m.stream, frames, sizeof frames, &dev); },
+                     [&] { return m.eager.calls == 0 && i == 0 && ring_consistent(m.eager, 8) && count_op(mark, MEMCPY) == 0; }))
+                return 1;
+            CHECK(m.eager.calls == i + 1 && dev == m.eager.dev[slot] && ring_consistent(m.eager, 8));
+            CHECK(std::memcmp(dev, frames, sizeof frames) == 0);
+            CHECK(live.size() == n_live + (i == 0 ? 24 : 0));  // all eight slots at the first call: no later call allocates
+            for (unsigned q = 0; q < 8; q++) CHECK(m.eager.made(q));
+            const long waited = find_op(mark, EVENT_SYNC, m.eager.event[slot]), copied = find_op(mark, MEMCPY, dev);
+            CHECK(count_op(mark, EVENT_SYNC) == (i >= 8 ? 1u : 0u) && copied >= 0 && (i < 8 || (waited >= 0 && waited < copied)));
+            CHECK(m.eager.done(m.stream) == SF_OK);
+            CHECK(calls.back().op == EVENT_RECORD && calls.back().p == m.eager.event[slot]);
+        }
+
+        // ---- an owner on the stack, left by an early return and by the last one
+        n_live = live.size();
+        if (step([&] { return call_local(true); }, [&] { return live.size() == n_live; })) return 1;
+        CHECK(live.size() == n_live);
+        if (step([&] { return call_local(false); }, [&] { return live.size() == n_live; })) return 1;
+        CHECK(live.size() == n_live);
+
+        // ---- one block back before the rest, then everything
+        m.own.free_device(m.in2);
+        m.in2 = nullptr;
+        CHECK(live.size() == n_live - 1);
+        m.own.release_all();
+        CHECK(live.empty());
+        CHECK(m.own.dev.empty() && m.own.pinned.empty() && m.own.events.empty() && m.own.streams.empty());
+    }  // (the destructor of an owner that has released everything does nothing: a second free would abort above)
+    CHECK(live.empty());
+    CHECK(failing == 0 || fired);
+    *acquiring_calls = acquired;
+    return 0;
+}
+
+int main() {
+    int n = 0, unused = 0;
+    if (scenario(0, &n)) return 1;
+    if (n < 40) {
+        std::printf("FAILED: only %d acquiring calls in the clean run\n", n);
+        return 1;
+    }
+    int runs = 1;
+    for (int k = 1; k <= n; k++, runs++)
+        if (scenario(k, &unused)) return 1;
+    std::printf("ok %d\n", runs);
+    return 0;
+}
