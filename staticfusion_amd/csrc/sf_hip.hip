@@ -242,6 +242,7 @@ void sf_destroy(sf_handle *h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     orphan_maps(h);  // maps outliving their handle: their memory is freed now, every later call on them fails cleanly
+    orphan_keyframe_dbs(h);  // and its keyframe databases (sf_hip_keyframes.hip)
     h->own.release_all();
     delete h;
 }

@@ -15,6 +15,8 @@
 //                      include/sf_view.h, symbols sfv_*)
 //   sf_hip_score.hip   poses scored against maps: frame-to-map agreement counts (sf_score.h; its interface is
 //                      include/sf_score.h, symbols sfs_*)
+//   sf_hip_keyframes.hip  place recognition: fern-coded keyframes that propose poses (sf_keyframes.h; its interface is
+//                      include/sf_keyframes.h, symbols sfk_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -120,6 +122,9 @@ struct sf_handle {
     unsigned char *score_scratch = nullptr;
     size_t score_bytes = 0;
     std::vector<unsigned char> score_tab_host, score_args_host;  // the host copies of the view table and the score table
+    // place recognition (sf_hip_keyframes.hip): live keyframe databases created from this handle: sf_destroy releases their
+    // memory and orphans them, like the maps
+    std::vector<struct sfk_db *> keyframe_dbs;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -212,6 +217,7 @@ struct ViewPlan {
 SF_INTERNAL void sfv_plan(ViewPlan &p, int n, const ViewJob *jobs, const struct sfv_view *views, int upload_count);
 SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const struct sfv_view *views, const ViewOut *outs,
                               unsigned char *base, std::vector<unsigned char> &tab_host, const float *upload, int upload_count);
+SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
