@@ -17,6 +17,8 @@
 //                      include/sf_score.h, symbols sfs_*)
 //   sf_hip_keyframes.hip  place recognition: fern-coded keyframes that propose poses (sf_keyframes.h; its interface is
 //                      include/sf_keyframes.h, symbols sfk_*)
+//   sf_hip_regions.hip moving regions: connected components of the dynamic pixels, numbered, with statistics
+//                      (sf_regions.h; its interface is include/sf_regions.h, symbols sfr_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -125,6 +127,12 @@ struct sf_handle {
     // place recognition (sf_hip_keyframes.hip): live keyframe databases created from this handle: sf_destroy releases their
     // memory and orphans them, like the maps
     std::vector<struct sfk_db *> keyframe_dbs;
+    // moving regions (sf_hip_regions.hip): one block for the entry table, the provisional label and count images, the block
+    // counts and -- for the host forms -- the uploaded frames, records and label images of a call, grown when a call needs
+    // more (dev_grow); the host copy the entry table is filled from
+    unsigned char *regions_scratch = nullptr;
+    size_t regions_bytes = 0;
+    std::vector<unsigned char> regions_args_host;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
