@@ -19,6 +19,8 @@
 //                      include/sf_keyframes.h, symbols sfk_*)
 //   sf_hip_regions.hip moving regions: connected components of the dynamic pixels, numbered, with statistics
 //                      (sf_regions.h; its interface is include/sf_regions.h, symbols sfr_*)
+//   sf_hip_align.hip   poses refined against maps: damped point-to-plane steps with integer normal equations
+//                      (sf_align.h, sf_align_step.h; its interface is include/sf_align.h, symbols sfa_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,6 +135,12 @@ struct sf_handle {
     unsigned char *regions_scratch = nullptr;
     size_t regions_bytes = 0;
     std::vector<unsigned char> regions_args_host;
+    // pose refinement (sf_hip_align.hip): a block of its own with the drawing layout (ViewPlan) followed by the entry table
+    // with the entries' states, the model images, the systems, the result records and -- for the host-pointer calls -- the
+    // uploaded frames; the host copies of the view table and the entry table
+    unsigned char *align_scratch = nullptr;
+    size_t align_bytes = 0;
+    std::vector<unsigned char> align_tab_host, align_args_host;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)

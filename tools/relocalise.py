@@ -24,8 +24,8 @@ from staticfusion_amd import keyframes, score, view
 from staticfusion_amd.synth import Scene, pose_delta, se3_exp
 
 
-def main():
-    ap = argparse.ArgumentParser()
+def arguments(doc=None):
+    ap = argparse.ArgumentParser(description=doc)
     ap.add_argument("--frames", type=int, default=14)
     ap.add_argument("--lost-stream", type=int, default=1)
     ap.add_argument("--earlier-frame", type=int, default=4)
@@ -34,7 +34,12 @@ def main():
     ap.add_argument("--ferns", type=int, default=256)
     ap.add_argument("--step-scale", type=float, default=2.0, help="the walk's step as a multiple of the one of tools/track_health.py")
     ap.add_argument("--json", default=None)
-    a = ap.parse_args()
+    return ap
+
+
+def lost_in_the_rooms(a):
+    """the walk, the keyframe database and the lost stream (also the scene of tools/refine_pose.py): solver, maps, what the
+    database holds, the lost stream and the frame it was handed, the true poses, the candidates of ONE query and their views"""
     api = sf.load()
     rows, cols, res, n = 240, 320, 2, 4
     s = sf.Solver(api, rows, cols, n, api.default_params_struct())
@@ -97,6 +102,12 @@ def main():
         v = view.default_view(s, maps[lost])
         v.pose[:] = [float(x) for x in pose.T.ravel()]
         vs.append(v)
+    return s, maps, info, stored, lost, k0, gts, cand, vs
+
+
+def main():
+    a = arguments().parse_args()
+    s, maps, info, stored, lost, k0, gts, cand, vs = lost_in_the_rooms(a)
     rec = score.score_streams([maps[lost]] * len(vs), vs, [lost] * len(vs), score.Params(use_b=False))  # (the b image belongs to another frame)
     d = score.derived(rec)
     winner = int(np.argmax(rec["n_inlier"]))
