@@ -21,6 +21,8 @@
 //                      (sf_regions.h; its interface is include/sf_regions.h, symbols sfr_*)
 //   sf_hip_align.hip   poses refined against maps: damped point-to-plane steps with integer normal equations
 //                      (sf_align.h, sf_align_step.h; its interface is include/sf_align.h, symbols sfa_*)
+//   sf_hip_join.hip    maps joined and thinned on a voxel grid: merge, decimate (sf_join.h, sf_join_key.h; its interface
+//                      is include/sf_join.h, symbols sfj_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -141,6 +143,12 @@ struct sf_handle {
     unsigned char *align_scratch = nullptr;
     size_t align_bytes = 0;
     std::vector<unsigned char> align_tab_host, align_args_host;
+    // joined and thinned maps (sf_hip_join.hip): one block for the two entry tables, the counters, the voxel tables, the
+    // remembered slots, the ballots and the block counts of a call, grown when a call needs more (dev_grow); the host copy
+    // the tables are filled from
+    unsigned char *join_scratch = nullptr;
+    size_t join_bytes = 0;
+    std::vector<unsigned char> join_args_host;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
