@@ -23,6 +23,8 @@
 //                      (sf_align.h, sf_align_step.h; its interface is include/sf_align.h, symbols sfa_*)
 //   sf_hip_join.hip    maps joined and thinned on a voxel grid: merge, decimate (sf_join.h, sf_join_key.h; its interface
 //                      is include/sf_join.h, symbols sfj_*)
+//   sf_hip_tracks.hip  region tracks: the moving regions followed from frame to frame, with a metric box (sf_tracks.h,
+//                      sf_track_assign.h; its interface is include/sf_tracks.h, symbols sft_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -149,6 +151,9 @@ struct sf_handle {
     unsigned char *join_scratch = nullptr;
     size_t join_bytes = 0;
     std::vector<unsigned char> join_args_host;
+    // region tracks (sf_hip_tracks.hip): live trackers created from this handle. Their state and scratch are blocks of `own`;
+    // sf_destroy releases them with it and orphans the trackers, like the keyframe databases
+    std::vector<struct sft_tracker *> trackers;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -242,6 +247,7 @@ SF_INTERNAL void sfv_plan(ViewPlan &p, int n, const ViewJob *jobs, const struct 
 SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const struct sfv_view *views, const ViewOut *outs,
                               unsigned char *base, std::vector<unsigned char> &tab_host, const float *upload, int upload_count);
 SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
+SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
