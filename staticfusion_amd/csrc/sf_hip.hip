@@ -239,6 +239,7 @@ static int validate_params(const sf_params *p, int levels) {
 // (orphan_maps: sf_hip_model.hip)
 void sf_destroy(sf_handle *h) {
     if (!h) return;
+    handle_gone(h);  // (sf_hip_bodies.hip)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     orphan_maps(h);  // maps outliving their handle: their memory is freed now, every later call on them fails cleanly
@@ -451,6 +452,7 @@ int sf_create_ex(const sf_params *p, int rows, int cols, int batch, int device, 
         std::vector<float> half(B * N0, 0.5f);  // b_segm_perpixel.fill(0.5f)
         HIP_OR_FREE(hipMemcpy(k.b_img, half.data(), B * N0 * sizeof(float), hipMemcpyHostToDevice));
     }
+    handle_born(h);
     *out = h;
     return SF_OK;
 }

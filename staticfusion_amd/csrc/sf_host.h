@@ -25,6 +25,8 @@
 //                      is include/sf_join.h, symbols sfj_*)
 //   sf_hip_tracks.hip  region tracks: the moving regions followed from frame to frame, with a metric box (sf_tracks.h,
 //                      sf_track_assign.h; its interface is include/sf_tracks.h, symbols sft_*)
+//   sf_hip_bodies.hip  region motion: the rigid motion of every moving region between two frames (sf_bodies.h,
+//                      sf_body_world.h; its interface is include/sf_bodies.h, symbols sfb_*); the list of live handles
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -154,6 +156,13 @@ struct sf_handle {
     // region tracks (sf_hip_tracks.hip): live trackers created from this handle. Their state and scratch are blocks of `own`;
     // sf_destroy releases them with it and orphans the trackers, like the keyframe databases
     std::vector<struct sft_tracker *> trackers;
+    // region motion (sf_hip_bodies.hip): one block for the entry table, the pair table, the region states, the systems, the
+    // model images and -- for the host form -- the uploaded frames and the results of a call, grown when a call needs more
+    // (dev_grow); the host copies the two tables are filled from
+    unsigned char *bodies_scratch = nullptr;
+    size_t bodies_bytes = 0;
+    std::vector<unsigned char> bodies_args_host;
+    std::vector<int32_t> bodies_pairs_host;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -248,6 +257,10 @@ SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jo
                               unsigned char *base, std::vector<unsigned char> &tab_host, const float *upload, int upload_count);
 SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
 SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
+// sf_hip_bodies.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the region
+// motion calls refuse a destroyed handle
+SF_INTERNAL void handle_born(const sf_handle *h);
+SF_INTERNAL void handle_gone(const sf_handle *h);
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
