@@ -41,7 +41,7 @@ void handle_gone(const sf_handle *h) {
     auto &v = live_handles();
     v.erase(std::remove(v.begin(), v.end(), h), v.end());
 }
-static bool handle_alive(const sf_handle *h) {
+bool handle_alive(const sf_handle *h) {
     std::lock_guard<std::mutex> g(live_mutex());
     const auto &v = live_handles();
     return std::find(v.begin(), v.end(), h) != v.end();

@@ -27,6 +27,8 @@
 //                      sf_track_assign.h; its interface is include/sf_tracks.h, symbols sft_*)
 //   sf_hip_bodies.hip  region motion: the rigid motion of every moving region between two frames (sf_bodies.h,
 //                      sf_body_world.h; its interface is include/sf_bodies.h, symbols sfb_*); the list of live handles
+//   sf_hip_body_maps.hip  body maps: every moving region fused into a surfel map of its own (sf_body_maps.h,
+//                      sf_body_map_rules.h; its interface is include/sf_body_maps.h, symbols sfp_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -163,6 +165,12 @@ struct sf_handle {
     size_t bodies_bytes = 0;
     std::vector<unsigned char> bodies_args_host;
     std::vector<int32_t> bodies_pairs_host;
+    // body maps (sf_hip_body_maps.hip): one block for the two entry tables, the counters, the voxel tables with their bids, the
+    // candidates' slots, the merge table, the ballots, the block counts and -- for the host form -- the uploaded frames of a
+    // call, grown when a call needs more (dev_grow); the host copy the tables are filled from
+    unsigned char *body_maps_scratch = nullptr;
+    size_t body_maps_bytes = 0;
+    std::vector<unsigned char> body_maps_args_host;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -258,9 +266,10 @@ SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jo
 SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
 SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
 // sf_hip_bodies.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the region
-// motion calls refuse a destroyed handle
+// motion calls and the body map calls refuse a destroyed handle
 SF_INTERNAL void handle_born(const sf_handle *h);
 SF_INTERNAL void handle_gone(const sf_handle *h);
+SF_INTERNAL bool handle_alive(const sf_handle *h);
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
