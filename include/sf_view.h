@@ -16,7 +16,9 @@
  *   - the surfel is culled when h.z > max_depth, h.z < 0.4f, s[3] < min_confidence, or (max_age >= 0 and not
  *     (float)tick - s[7] <= (float)max_age); a comparison with a NaN operand is false;
  *   - a surfel whose centre projects outside the image is not drawn (splat.vert); the sprite is the square around the
- *     centre whose side is the longer extent of the four projected corners;
+ *     centre whose side is the longer extent of the four projected corners; while all four corners have z > 0 only the
+ *     pixels of their bounding rectangle (widened by one pixel) are visited, which loses no fragment (the disc lies inside
+ *     the diamond of the corners); a surfel with a corner at z <= 0 keeps the whole square;
  *   - per fragment: the view ray of the pixel centre meets the surfel's plane; the fragment is kept inside the disc of
  *     radius s[11], with depth = z / (2 max_depth) + 0.5 kept when 0 <= depth < 1;
  *   - the smallest (depth, surfel index) wins a pixel, so the earlier surfel wins an exact tie.

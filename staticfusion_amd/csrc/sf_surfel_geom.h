@@ -82,9 +82,14 @@ __device__ __forceinline__ bool surfel_sprite(const A &a, PV3 h, PV3 n, float ra
     j0 = max(0, (int)ceilf(yw - half - 0.5f)); j1 = min(a.rows - 1, (int)floorf(yw + half - 0.5f));
     // The sprite is a SQUARE of the longer extent (splat.vert:85), but a fragment survives only inside the disc
     // (combo_splat.frag:47), and the disc lies inside the diamond whose corners were just projected: pixels outside
-    // their bounding rectangle (+ 1 pixel against rounding at the rim) would be discarded anyway -- skip them.
-    i0 = max(i0, (int)floorf(xlo - 1.5f)); i1 = min(i1, (int)ceilf(xhi + 0.5f));
-    j0 = max(j0, (int)floorf(ylo - 1.5f)); j1 = min(j1, (int)ceilf(yhi + 0.5f));
+    // their bounding rectangle (+ 1 pixel against rounding at the rim) would be discarded anyway -- skip them. That
+    // holds only while all four corners lie in front of the camera: the projection of a corner with z <= 0 is mirrored
+    // and the rectangle no longer contains the disc's image (a tilted disc with rad sqrt(2) above the depth of its
+    // centre). Such a surfel keeps the whole square, as the shaders draw it.
+    if (c1.z > 0.f && c2.z > 0.f && c3.z > 0.f && c4.z > 0.f) {
+        i0 = max(i0, (int)floorf(xlo - 1.5f)); i1 = min(i1, (int)ceilf(xhi + 0.5f));
+        j0 = max(j0, (int)floorf(ylo - 1.5f)); j1 = min(j1, (int)ceilf(yhi + 0.5f));
+    }
     return i0 <= i1 && j0 <= j1;
 }
 

@@ -100,6 +100,35 @@ def test_hip_equals_the_oracles_prediction(hip_auto, ora, rows, cols):
     so.close()
 
 
+def test_hip_equals_the_oracles_prediction_of_discs_that_cross_the_camera_plane(hip_auto, ora):
+    """tilted discs with rad sqrt(2) above the depth of their centre, among 500 small surfels (surfel_cases.crossing): a corner
+    of their diamond lies behind the camera, its projection is mirrored, and the bounding rectangle of the corners does not
+    hold the disc's image -- the oracle, like the shaders, has no such rectangle"""
+    import surfel_cases as sc
+
+    case = sc.crossing()
+    rows, cols = case.rows, case.cols
+    so = make_solver(ora, rows, cols, driver_params(ora))
+    sh = small_solver(hip_auto, rows, cols)
+    preds = []
+    for s in (so, sh):
+        vc.prime_pure_render(s, rows, cols)
+        mp = vc.pure_render_params(s, dict(cx=case.cx, cy=case.cy, fx=case.fx, fy=case.fy), case.min_confidence, case.max_depth, time=case.tick)
+        s.predict_from_model(0, case.surfels, case.pose, mp)
+        preds.append(s.prediction())
+    (d, inten), (dh, ih) = preds
+    assert same_bits(dh, d) and same_bits(ih, inten)
+    v = vc.view_of(mp, case.pose, rows, cols)
+    got = view.render_surfels(sh, case.surfels, v, tick=case.tick)
+    assert view.last_large_sprites(sh, 1) == [len(case.big)]
+    assert same_images(got, view_ref.render(case.surfels, v, tick=case.tick))
+    assert same_bits(np.where(got["depth"] > 0, got["depth"], np.float32(0)), d) and same_bits(view_ref.grey(got["rgb"]), inten)  # (no clip at z <= 0 in a view)
+    won = np.isin(got["index"], case.big)
+    assert won.mean() > 0.5 and (got["index"] >= 0).mean() > 0.9 and (~won & (got["index"] >= 0)).any()
+    sh.close()
+    so.close()
+
+
 # ---- 2. against NumPy, at sizes the oracle cannot take ---------------------------------------------------------------
 VIEWS = [(1, 1, 0.5, 0.5, 1.3, 1.1), (37, 53, 25.25, 19.5, 47.0, -44.0), (48, 64, 30.5, 25.0, 61.0, 58.5)]  # rows, cols, cx, cy, fx, fy
 

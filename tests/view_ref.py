@@ -11,6 +11,8 @@ import numpy as np
 F = np.float32
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 LARGE_PIXELS = 1024  # SFV_LARGE_PIXELS: a clipped sprite with more pixels is drawn by the large-sprite kernel
+SQRT2 = F(1.41421356)  # splat.vert:70
+PIXEL_CENTRE = F(0.5)  # gl_FragCoord of pixel i is i + 0.5
 
 
 def invert_pose(pose16):
@@ -73,13 +75,37 @@ class _Ctx:
         self.tick, self.max_age = F(tick), F(view.max_age)
         self.shade = int(view.shade)
         # the ray table, [i (column), j (row)]: normalize((i + 0.5 - cx) / fx, (j + 0.5 - cy) / fy, 1)
-        i = np.arange(self.cols, dtype=np.float32)[:, None] + F(0.5)
-        j = np.arange(self.rows, dtype=np.float32)[None, :] + F(0.5)
+        i = np.arange(self.cols, dtype=np.float32)[:, None] + PIXEL_CENTRE
+        j = np.arange(self.rows, dtype=np.float32)[None, :] + PIXEL_CENTRE
         X = np.broadcast_to((i - self.cx) / self.fx, (self.cols, self.rows))
         Y = np.broadcast_to((j - self.cy) / self.fy, (self.cols, self.rows))
         Z = np.ones((self.cols, self.rows), np.float32)
         n = np.sqrt((X * X + Y * Y) + Z * Z)
         self.rays = (X / n, Y / n, Z / n)
+        self.rays_of_the_dot = _rays_of_the_dot(self.rays, (X, Y, Z))
+
+
+def _rays_of_the_dot(normalised, unnormalised):
+    """the ray dot(l, n) is taken with: the normalised one (combo_splat.frag:37-39)"""
+    return normalised
+
+
+def _corner_rectangle_applies(corners):
+    """the corner rectangle prunes only while every corner is in front of the camera (sf_surfel_geom.h, surfel_sprite)"""
+    return all(p[2] > F(0) for p in corners)
+
+
+def _discarded(dd, r2):
+    return dd > r2  # combo_splat.frag:45
+
+
+def _key(depth, s):
+    """GL_LESS in buffer order: the smallest (depth bits, index) wins"""
+    return (depth.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(s)
+
+
+def _index_of(keys):
+    return keys & np.uint64(0xFFFFFFFF)
 
 
 def _to_camera(c, q):
@@ -106,7 +132,7 @@ def _sprite(c, q):
         return None
     xw, yw = (ndc_x + F(1)) * (fcols * F(0.5)), (ndc_y + F(1)) * (frows * F(0.5))
     u = _normalize((n[1] - n[2], -n[0], n[0]))
-    x1 = tuple((a * rad) * F(1.41421356) for a in u)
+    x1 = tuple((a * rad) * SQRT2 for a in u)
     y1 = _cross(n, x1)
     corners = [tuple(a + b for a, b in zip(h, x1)), tuple(a + b for a, b in zip(h, y1)), tuple(a - b for a, b in zip(h, y1)),
                tuple(a - b for a, b in zip(h, x1))]
@@ -124,10 +150,11 @@ def _sprite(c, q):
     i1 = min(c.cols - 1, _to_int(np.floor(xw + half - F(0.5))))
     j0 = max(0, _to_int(np.ceil(yw - half - F(0.5))))
     j1 = min(c.rows - 1, _to_int(np.floor(yw + half - F(0.5))))
-    i0 = max(i0, _to_int(np.floor(xlo - F(1.5))))
-    i1 = min(i1, _to_int(np.ceil(xhi + F(0.5))))
-    j0 = max(j0, _to_int(np.floor(ylo - F(1.5))))
-    j1 = min(j1, _to_int(np.ceil(yhi + F(0.5))))
+    if _corner_rectangle_applies(corners):
+        i0 = max(i0, _to_int(np.floor(xlo - F(1.5))))
+        i1 = min(i1, _to_int(np.ceil(xhi + F(0.5))))
+        j0 = max(j0, _to_int(np.floor(ylo - F(1.5))))
+        j1 = min(j1, _to_int(np.ceil(yhi + F(0.5))))
     if not (i0 <= i1 and j0 <= j1):
         return None
     return h, n, rad, i0, i1, j0, j1
@@ -175,19 +202,20 @@ def render(surfels, view, tick=1):
             h, n, rad, i0, i1, j0, j1 = sp
             win = (slice(i0, i1 + 1), slice(j0, j1 + 1))
             lx, ly, lz = c.rays[0][win], c.rays[1][win], c.rays[2][win]
-            t = _dot(h, n) / ((lx * n[0] + ly * n[1]) + lz * n[2])
+            dx_, dy_, dz_ = (r[win] for r in c.rays_of_the_dot)
+            t = _dot(h, n) / ((dx_ * n[0] + dy_ * n[1]) + dz_ * n[2])
             cx_, cy_, cz_ = lx * t, ly * t, lz * t
             dx, dy, dz = cx_ - h[0], cy_ - h[1], cz_ - h[2]
-            keep = ~(((dx * dx + dy * dy) + dz * dz) > rad * rad)
+            keep = ~_discarded((dx * dx + dy * dy) + dz * dz, rad * rad)
             depth = (cz_ / two_max) + F(0.5)
             keep &= (depth >= F(0)) & (depth < F(1))
-            key = (depth.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(s)
+            key = _key(depth, s)
             better = keep & (key < keys[win])
             keys[win] = np.where(better, key, keys[win])
             zimg[win] = np.where(better, cz_, zimg[win])
             nimg[win] = np.where(better[..., None], np.array(n, np.float32), nimg[win])
         drawn = keys != EMPTY
-        index = np.where(drawn, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+        index = np.where(drawn, _index_of(keys).astype(np.int64), -1).astype(np.int32)
         if c.shade == 1:
             v = np.fmin(np.fmax(F(0.5) * nimg + F(0.5), F(0)), F(1)) * F(255)
             rgb = np.rint(v).astype(np.int32).astype(np.uint8)
