@@ -25,11 +25,9 @@
 #include "sf_join_key.h"
 #include "sf_records.h"
 
-// The scan is that of sf_map_window.h, the same text, included into a namespace as sf_join.h does: its scan kernel is not a
-// template, host_map_window.o defines it for the library, and a second definition of that name would not link.
-namespace sfp_window {
-#include "sf_map_window.h"
-}
+// The scan is that of sf_map_window.h, launched by sfw_launch_scan (sf_host.h): the host fills a WindowArgs beside every
+// BodyMapArgs.
+#include "sf_window_args.h"
 
 #define SFP_BLOCK SFW_BLOCK
 #define SFP_WAVES SFW_WAVES

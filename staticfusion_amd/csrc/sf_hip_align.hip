@@ -1,11 +1,10 @@
 // sf_hip_align.hip — libsf_hip.so, the interface of include/sf_align.h (symbols sfa_*): damped point-to-plane refinement of
 // many (map, candidate pose, frame) entries per call (kernels: sf_align.h; the step: sf_align_step.h). The maps are drawn by
-// the drawing stage of the views (sfv_plan / sfv_draw_keys of sf_hip_view.hip) into a block of the refine calls' own
-// (sf_handle::align_scratch, grown when a call needs more and freed with the handle); behind the drawing layout lie the
-// entry table with the entries' states, the model images, the systems, the result records and -- for the host-pointer
-// calls -- the uploaded frames. A refine call only reads its maps and streams and leaves the view scratch, and with it
-// sfv_last_large_sprites, and the scratch of the score and region calls alone. The number of launches is fixed by the
-// largest `iterations` of the call; nothing is read back between them.
+// the drawing stage of the views (sfv_plan / sfv_draw_keys of sf_hip_view.hip) into the call block sf_handle::align
+// (sf_call_block.h: layout, growth and lifetime); behind the drawing layout lie the entry table with the entries' states, the
+// model images, the systems, the result records and -- for the host-pointer calls -- the uploaded frames. A refine call only
+// reads its maps and streams. The number of launches is fixed by the largest `iterations` of the call; nothing is read back
+// between them.
 #include "../../include/sf_align.h"
 #include "sf_host.h"
 #include "sf_align.h"
@@ -17,10 +16,10 @@ static_assert(sizeof(sfa_system) == 256 && sizeof(sfa_system) == SFA_SYSTEM_WORD
               "sfa_linearise_kernel adds the first 29 int64 fields of a sfa_system");
 static_assert(SFA_STEP_OK == SFA_OK && SFA_STEP_DEGENERATE == SFA_DEGENERATE, "sf_align_step.h restates the status codes");
 
+static_assert(offsetof(sfa_params, damping) == 12, "the four floats of sfa_params are consecutive");
 static int check_params(const sfa_params *p) {
     if (!p) return fail(SF_ERR_ARG, "sfa: null params");
-    if (!(std::isfinite(p->dist_max) && std::isfinite(p->z_max) && std::isfinite(p->b_min) && std::isfinite(p->damping)))
-        return fail(SF_ERR_ARG, "sfa: NaN or inf in sfa_params");
+    if (!finite_all(&p->dist_max, 4)) return fail(SF_ERR_ARG, "sfa: NaN or inf in sfa_params");
     if (!(p->dist_max > 0.f && p->dist_max <= 1.f)) return fail(SF_ERR_ARG, "sfa: dist_max lies in (0, 1]");
     if (!(p->z_max > 0.f && p->z_max <= 32.f)) return fail(SF_ERR_ARG, "sfa: z_max lies in (0, 32]");
     if (p->damping < 0.f) return fail(SF_ERR_ARG, "sfa: a negative damping");
@@ -31,17 +30,15 @@ static int check_params(const sfa_params *p) {
     return SF_OK;
 }
 
-enum AlignForm { FORM_STREAMS, FORM_HOST, FORM_DEVICE };
-
 // every check of the refusal list, then: plan, grow, upload, draw, model images, the fixed sequence of linearisations and
 // steps, and for the host forms the copies back
-static int refine(const char *what, AlignForm form, sf_handle *h, int n, sf_map *const *maps, const sfv_view *views, const int32_t *streams,
+static int refine(const char *what, CallForm form, sf_handle *h, int n, sf_map *const *maps, const sfv_view *views, const int32_t *streams,
                   const void *const *depth, const void *const *b, const sfa_params *params, void *results, void *systems_out) {
     const std::string w(what);
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
     if (n == 0) return SF_OK;
     if (!maps || !views || !params || !results || (form == FORM_STREAMS ? !streams : !depth)) return fail(SF_ERR_ARG, w + ": null argument");
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
+    if (int e = check_batch(w, n)) return e;
     std::vector<ViewJob> jobs((size_t)n);
     int max_it = 0;
     for (int q = 0; q < n; q++) {
@@ -82,12 +79,11 @@ static int refine(const char *what, AlignForm form, sf_handle *h, int n, sf_map 
             if (params[q].use_b) o_b[(size_t)q] = p.take(px * 4);
         }
     }
-    if (int e = dev_grow(h, &h->align_scratch, &h->align_bytes, p.off)) return e;
-    unsigned char *base = h->align_scratch;
-    // ---- the entry table and the states
-    h->align_args_host.assign(tab_bytes, 0);  // (a member, like the view table: it outlives an asynchronous call)
-    AlignArgs *atab = (AlignArgs *)h->align_args_host.data();
-    AlignState *states = (AlignState *)(h->align_args_host.data() + (size_t)n * sizeof(AlignArgs));
+    if (int e = h->align.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->align.dev;
+    // ---- the entry table and the states (host copy 1, zeroed: a state starts from zeros; the view table is copy 0)
+    AlignArgs *atab = (AlignArgs *)h->align.zeroed<unsigned char>(tab_bytes, 1);
+    AlignState *states = (AlignState *)(atab + n);
     sfa_result *d_res = form == FORM_DEVICE ? (sfa_result *)results : (sfa_result *)(base + o_res);
     long long *d_sys = (form == FORM_DEVICE && systems_out) ? (long long *)systems_out : (long long *)(base + o_sys);
     for (int q = 0; q < n; q++) {
@@ -116,10 +112,10 @@ static int refine(const char *what, AlignForm form, sf_handle *h, int n, sf_map 
         s.result = d_res + q;
         states[(size_t)q].D[0] = states[(size_t)q].D[5] = states[(size_t)q].D[10] = 1.0;  // D0 = I
     }
-    HIP_TRY(hipMemcpyAsync(base + o_atab, atab, tab_bytes, hipMemcpyHostToDevice, h->stream));
+    if (int e = h->align.upload(o_atab, atab, tab_bytes, h->stream)) return e;
     HIP_TRY(hipMemsetAsync(d_sys, 0, sys_bytes, h->stream));
     // ---- draw the keys, resolve the model images, then the fixed sequence
-    if (int e = sfv_draw_keys(h, p, jobs.data(), views, nullptr, base, h->align_tab_host, nullptr, 0)) return e;
+    if (int e = sfv_draw_keys(h, p, jobs.data(), views, nullptr, h->align, nullptr, 0)) return e;
     const ViewArgs *d_vtab = (const ViewArgs *)(base + p.o_tab);
     const AlignArgs *d_atab = (const AlignArgs *)(base + o_atab);
     hipLaunchKernelGGL(sfa_model_kernel, dim3((unsigned)((max_px + 255) / 256), (unsigned)n), dim3(256), 0, h->stream, d_vtab, d_atab);

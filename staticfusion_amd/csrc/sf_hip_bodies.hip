@@ -1,10 +1,10 @@
 // sf_hip_bodies.hip — libsf_hip.so, the interface of include/sf_bodies.h (symbols sfb_*): the rigid motion of every moving
 // region of a batch of frame pairs, by damped point-to-plane steps (kernels: sf_bodies.h; the step: sf_align_step.h; the world
-// motion: sf_body_world.h). Everything a call needs is one block of the handle (sf_handle::bodies_scratch, grown when a call
-// needs more and freed with the handle): the entry table, the pair table, the region states, the model images, the systems
-// and -- for the host form -- the uploaded frames and the results. A call only reads its inputs and leaves the scratch of
-// every other companion alone. The number of launches is fixed by the largest `iterations` of the call; nothing is read back
-// between them. This file also keeps the list of live handles, which is how a call on a destroyed handle is refused.
+// motion: sf_body_world.h). Everything a call needs lies in the call block sf_handle::bodies (sf_call_block.h: layout, growth
+// and lifetime): the entry table, the pair table, the region states, the model images, the systems and -- for the host form --
+// the uploaded frames and the results. A call only reads its inputs. The number of launches is fixed by the largest
+// `iterations` of the call; nothing is read back between them. This file also keeps the list of live handles, which is how a
+// call on a destroyed handle is refused.
 #include "../../include/sf_bodies.h"
 #include "sf_host.h"
 #include "sf_bodies.h"
@@ -47,16 +47,10 @@ bool handle_alive(const sf_handle *h) {
     return std::find(v.begin(), v.end(), h) != v.end();
 }
 
-static bool finite_all(const float *p, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
+static_assert(offsetof(sfb_params, damping) == 12, "the four floats of sfb_params are consecutive");
 static int check_params(const sfb_params *p) {
     if (!p) return fail(SF_ERR_ARG, "sfb: null params");
-    if (!(std::isfinite(p->dist_max) && std::isfinite(p->z_max) && std::isfinite(p->normal_dz) && std::isfinite(p->damping)))
-        return fail(SF_ERR_ARG, "sfb: NaN or inf in sfb_params");
+    if (!finite_all(&p->dist_max, 4)) return fail(SF_ERR_ARG, "sfb: NaN or inf in sfb_params");
     if (!(p->dist_max > 0.f && p->dist_max <= 1.f)) return fail(SF_ERR_ARG, "sfb: dist_max lies in (0, 1]");
     if (!(p->z_max > 0.f && p->z_max <= 32.f)) return fail(SF_ERR_ARG, "sfb: z_max lies in (0, 32]");
     if (!(p->normal_dz > 0.f && p->normal_dz <= 32.f)) return fail(SF_ERR_ARG, "sfb: normal_dz lies in (0, 32]");
@@ -65,21 +59,6 @@ static int check_params(const sfb_params *p) {
     if (p->min_pairs < 6) return fail(SF_ERR_ARG, "sfb: min_pairs is at least 6");
     return SF_OK;
 }
-
-static int check_camera(const sfb_camera *c) {
-    if (!finite_all(c->pose, 16) || !finite_all(&c->cx, 4)) return fail(SF_ERR_ARG, "sfb: NaN or inf in a camera");
-    if (c->fx == 0.f || c->fy == 0.f) return fail(SF_ERR_ARG, "sfb: fx or fy is 0");
-    return SF_OK;
-}
-
-struct BodyPlan {
-    size_t off = 0;
-    size_t take(size_t bytes) {  // 256-byte aligned
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
 
 // every check of the refusal list, then: plan, grow, upload, the model images, the fixed sequence of linearisations and steps,
 // and for the host form the copies back
@@ -90,10 +69,9 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
     if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
+    if (int e = check_batch(w, n)) return e;
     if (!depth0 || !labels0 || !depth1 || !cams0 || !cams1 || !n_regions || !params || !motions) return fail(SF_ERR_ARG, w + ": null argument");
-    if (rows < 1 || rows > 4096 || cols < 1 || cols > 4096 || (long long)rows * cols > (1ll << 24))
-        return fail(SF_ERR_ARG, w + ": rows and cols lie in 1..4096 and rows * cols <= 2^24");
+    if (int e = check_image_size(w, rows, cols)) return e;
     if (max_regions < 1 || max_regions > SFB_MAX_REGIONS) return fail(SF_ERR_ARG, w + ": max_regions lies in 1..256");
     const int M = max_regions;
     int max_it = 0;
@@ -108,8 +86,8 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
                 if (want != 0 && t < n_regions[q] && !have_l1) return fail(SF_ERR_ARG, w + ": a pair without the label image of frame 1");
             }
         }
-        if (int e = check_camera(cams0 + q)) return e;
-        if (int e = check_camera(cams1 + q)) return e;
+        if (int e = check_camera("sfb", cams0 + q)) return e;
+        if (int e = check_camera("sfb", cams1 + q)) return e;
         if (int e = check_params(params + q)) return e;
         max_it = std::max(max_it, params[q].iterations);
     }
@@ -118,7 +96,7 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
     const size_t px = (size_t)rows * cols, slots_total = (size_t)n * M;
     const int sys_slots = systems_out ? max_it + 1 : 1;  // unless the systems are an output, one record per region slot is reused
     const size_t sys_bytes = slots_total * (size_t)sys_slots * sizeof(sfb_system);
-    BodyPlan p;
+    SfPlan p;
     const size_t o_args = p.take((size_t)n * sizeof(BodyArgs));
     const size_t o_pairs = pairs ? p.take(slots_total * 4) : 0;
     const size_t o_state = p.take(slots_total * sizeof(BodyState));
@@ -127,11 +105,10 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
     const size_t o_model = p.take((size_t)n * px * 2 * sizeof(vfloat4));
     size_t o_up = 0;
     if (!device_form) o_up = p.take((size_t)n * 4 * px * 4);  // depth0, labels0, depth1, labels1 of every entry
-    if (int e = dev_grow(h, &h->bodies_scratch, &h->bodies_bytes, p.off)) return e;
-    unsigned char *base = h->bodies_scratch;
-    // ---- the entry table
-    h->bodies_args_host.assign((size_t)n * sizeof(BodyArgs), 0);  // (a member: it outlives an asynchronous call)
-    BodyArgs *tab = (BodyArgs *)h->bodies_args_host.data();
+    if (int e = h->bodies.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->bodies.dev;
+    // ---- the entry table (host copy 0, zeroed) and the pair table (host copy 1)
+    BodyArgs *tab = h->bodies.zeroed<BodyArgs>((size_t)n);
     for (int q = 0; q < n; q++) {
         BodyArgs &a = tab[(size_t)q];
         const sfb_params &sp = params[q];
@@ -167,10 +144,11 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
     BodyState *d_state = (BodyState *)(base + o_state);
     long long *d_sys = (device_form && systems_out) ? (long long *)systems_out : (long long *)(base + o_sys);
     sfb_motion *d_mot = device_form ? (sfb_motion *)motions : (sfb_motion *)(base + o_mot);
-    HIP_TRY(hipMemcpyAsync(base + o_args, tab, (size_t)n * sizeof(BodyArgs), hipMemcpyHostToDevice, h->stream));
+    if (int e = h->bodies.upload(o_args, tab, (size_t)n * sizeof(BodyArgs), h->stream)) return e;
     if (pairs) {
-        h->bodies_pairs_host.assign(pairs, pairs + slots_total);
-        HIP_TRY(hipMemcpyAsync(base + o_pairs, h->bodies_pairs_host.data(), slots_total * 4, hipMemcpyHostToDevice, h->stream));
+        int32_t *ptab = h->bodies.resized<int32_t>(slots_total, 1);
+        std::memcpy(ptab, pairs, slots_total * 4);
+        if (int e = h->bodies.upload(o_pairs, ptab, slots_total * 4, h->stream)) return e;
     }
     HIP_TRY(hipMemsetAsync(d_sys, 0, sys_bytes, h->stream));
     HIP_TRY(hipMemsetAsync(d_mot, 0, slots_total * sizeof(sfb_motion), h->stream));  // records K .. M - 1 stay zeros

@@ -1,10 +1,10 @@
 // sf_hip_body_maps.hip — libsf_hip.so, the interface of include/sf_body_maps.h (symbols sfp_*): every moving region fused into
 // a surfel map of its own, many per call (kernels: sf_body_maps.h; the per-surfel rules: sf_body_map_rules.h; key, rank and
 // hash: sf_join_key.h). The two entry tables, the counters, the voxel tables with their bids, the candidates' slots, the merge
-// table, the ballots, the block counts and -- for the host form -- the uploaded frames of a call lie in a block of these calls'
-// own (sf_handle::body_maps_scratch, grown when a call needs more and freed with the handle), so a call leaves the scratch of
-// every other part alone. One host synchronisation reads the counts; it lies before the two passes that change a map, because
-// the capacity test needs them.
+// table, the ballots, the block counts and -- for the host form -- the uploaded frames of a call lie in the call block
+// sf_handle::body_maps (sf_call_block.h: layout, growth and lifetime); the scan is that of the bounded maps (sfw_launch_scan).
+// One host synchronisation reads the counts; it lies before the two passes that change a map, because the capacity test needs
+// them.
 #include "../../include/sf_body_maps.h"
 #include "sf_host.h"
 #include "sf_body_maps.h"
@@ -17,12 +17,6 @@ static_assert(sizeof(sfp_camera) == sizeof(sft_camera) && offsetof(sfp_camera, p
                   offsetof(sfp_camera, cy) == offsetof(sft_camera, cy) && offsetof(sfp_camera, fx) == offsetof(sft_camera, fx) &&
                   offsetof(sfp_camera, fy) == offsetof(sft_camera, fy) && sizeof(sfp_camera) == 80,
               "include/sf_body_maps.h: sfp_camera is the camera of include/sf_tracks.h");
-
-static bool finite_all(const float *p, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
 
 static int check_params(const sfp_params *p) {
     if (!p) return fail(SF_ERR_ARG, "sfp: null params");
@@ -39,39 +33,19 @@ static int check_params(const sfp_params *p) {
 }
 static_assert(offsetof(sfp_params, max_weight) == 24, "the seven floats of sfp_params are consecutive");
 
-static int check_camera(const sfp_camera *c) {
-    if (!finite_all(c->pose, 16) || !finite_all(&c->cx, 4)) return fail(SF_ERR_ARG, "sfp: NaN or inf in a camera");
-    if (c->fx == 0.f || c->fy == 0.f) return fail(SF_ERR_ARG, "sfp: fx or fy is 0");
-    return SF_OK;
-}
-
 // h is a live handle, the n maps are its own and distinct, W is finite
 static int check_maps(const std::string &w, sf_handle *h, int n, sf_map *const *maps, const float *W) {
     for (int q = 0; q < n; q++) {
         if (int e = check_map(w.c_str(), h, maps[q])) return e;
-        for (int r = 0; r < q; r++)
-            if (maps[r] == maps[q]) return fail(SF_ERR_ARG, w + ": the same map twice in one call");
+        if (int e = check_distinct(w, maps, q, "the same map twice in one call")) return e;
         if (W && !finite_all(W + (size_t)q * 16, 16)) return fail(SF_ERR_ARG, w + ": NaN or inf in W");
     }
     return SF_OK;
 }
 
-// where the parts of a call lie in the block
-struct BodyMapPlan {
-    size_t off = 0;
-    size_t take(size_t bytes) {  // 256-byte aligned
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 static void set_motion(BodyMapArgs &a, const float *W, int q) {
     for (int k = 0; k < 16; k++) a.W[k] = W ? W[(size_t)q * 16 + k] : (k % 5 == 0 ? 1.f : 0.f);
 }
-
-// the rule AFTER A CALL THAT CHANGES A MAP of include/sf_map_window.h
-static void indices_moved(sf_map *m) { m->have_index = false; }  // the index image of the last fuse no longer describes the map
 
 // every check of the refusal list, then: plan, grow, upload, insert, pixels, flag, scan, the counts, the capacity, the commit
 static int fuse(const char *what, bool device_form, sf_handle *h, int rows, int cols, int n, const void *const *depth, const void *const *labels,
@@ -81,14 +55,13 @@ static int fuse(const char *what, bool device_form, sf_handle *h, int rows, int 
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
     if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
+    if (int e = check_batch(w, n)) return e;
     if (!depth || !labels || !cams || !region_labels || !maps || !params || !counts_out) return fail(SF_ERR_ARG, w + ": null argument");
-    if (rows < 1 || rows > 4096 || cols < 1 || cols > 4096 || (long long)rows * cols > (1ll << 24))
-        return fail(SF_ERR_ARG, w + ": rows and cols lie in 1..4096 and rows * cols <= 2^24");
+    if (int e = check_image_size(w, rows, cols)) return e;
     for (int q = 0; q < n; q++) {
         if (!depth[q] || !labels[q]) return fail(SF_ERR_ARG, w + ": null image");
         if (region_labels[q] < 1) return fail(SF_ERR_ARG, w + ": a region label below 1");
-        if (int e = check_camera(cams + q)) return e;
+        if (int e = check_camera("sfp", cams + q)) return e;
         if (int e = check_params(params + q)) return e;
     }
     if (int e = check_maps(w, h, n, maps, W)) return e;
@@ -98,10 +71,10 @@ static int fuse(const char *what, bool device_form, sf_handle *h, int rows, int 
     const size_t px = (size_t)rows * cols;
     const size_t interior = (size_t)std::max(rows - 2, 0) * (size_t)std::max(cols - 2, 0);
     const size_t n_blocks = (px + SFP_BLOCK - 1) / SFP_BLOCK;
-    BodyMapPlan p;
-    const size_t tab_bytes = (size_t)n * (sizeof(sfp_window::WindowArgs) + sizeof(BodyMapArgs));
+    SfPlan p;
+    const size_t tab_bytes = (size_t)n * (sizeof(WindowArgs) + sizeof(BodyMapArgs));
     const size_t o_tab = p.take(tab_bytes);
-    const size_t o_zero = p.off;
+    p.zeros_from_here();
     const size_t o_counts = p.take((size_t)n * SFP_COUNT_WORDS * sizeof(int));
     std::vector<size_t> o_best((size_t)n), o_ballots((size_t)n), o_blocks((size_t)n), o_keys((size_t)n), o_bid((size_t)n), o_merge((size_t)n), o_cand((size_t)n);
     std::vector<int> slots((size_t)n);
@@ -115,22 +88,21 @@ static int fuse(const char *what, bool device_form, sf_handle *h, int rows, int 
         o_blocks[(size_t)q] = p.take((n_blocks + 1) * sizeof(int));
         max_count = std::max(max_count, maps[q]->count);
     }
-    const size_t o_ones = p.off;
+    p.ones_from_here();
     for (int q = 0; q < n; q++) {
         o_keys[(size_t)q] = p.take((size_t)slots[(size_t)q] * 8);
         o_bid[(size_t)q] = p.take((size_t)slots[(size_t)q] * 4);
         o_merge[(size_t)q] = p.take((size_t)maps[q]->count * sizeof(int));
     }
-    const size_t o_rest = p.off;
+    p.rest_from_here();
     for (int q = 0; q < n; q++) o_cand[(size_t)q] = p.take(px * sizeof(int));
     const size_t frame_bytes = (px * 4 + 255) / 256 * 256 * 2 + (px * 3 + 255) / 256 * 256;  // depth, labels, colour of an entry
     const size_t o_up = device_form ? 0 : p.take((size_t)n * frame_bytes);
-    if (int e = dev_grow(h, &h->body_maps_scratch, &h->body_maps_bytes, p.off)) return e;
-    unsigned char *base = h->body_maps_scratch;
-    // ---- the tables (a member holds the host copy: it outlives the asynchronous upload)
-    h->body_maps_args_host.assign(tab_bytes, 0);
-    sfp_window::WindowArgs *wtab = (sfp_window::WindowArgs *)h->body_maps_args_host.data();
-    BodyMapArgs *atab = (BodyMapArgs *)(h->body_maps_args_host.data() + (size_t)n * sizeof(sfp_window::WindowArgs));
+    if (int e = h->body_maps.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->body_maps.dev;
+    // ---- the tables, zeroed: one upload
+    WindowArgs *wtab = (WindowArgs *)h->body_maps.zeroed<unsigned char>(tab_bytes);
+    BodyMapArgs *atab = (BodyMapArgs *)(wtab + n);
     for (int q = 0; q < n; q++) {
         BodyMapArgs &a = atab[(size_t)q];
         const sfp_params &sp = params[q];
@@ -168,23 +140,22 @@ static int fuse(const char *what, bool device_form, sf_handle *h, int rows, int 
         a.ballots = (unsigned long long *)(base + o_ballots[(size_t)q]);
         a.block_counts = (int *)(base + o_blocks[(size_t)q]);
         a.counts = (int *)(base + o_counts) + (size_t)q * SFP_COUNT_WORDS;
-        sfp_window::WindowArgs &sw = wtab[(size_t)q];  // what the scan reads: the block counts over pixels
+        WindowArgs &sw = wtab[(size_t)q];  // what the scan reads: the block counts over pixels
         sw.count = (int)px;
         sw.ballots = a.ballots;
         sw.block_counts = a.block_counts;
         sw.result = a.counts + SFP_N_ADDED;
     }
-    HIP_TRY(hipMemcpyAsync(base + o_tab, h->body_maps_args_host.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(base + o_zero, 0, o_ones - o_zero, h->stream));
-    HIP_TRY(hipMemsetAsync(base + o_ones, 0xFF, o_rest - o_ones, h->stream));
-    const sfp_window::WindowArgs *dw = (const sfp_window::WindowArgs *)(base + o_tab);
-    const BodyMapArgs *da = (const BodyMapArgs *)(base + o_tab + (size_t)n * sizeof(sfp_window::WindowArgs));
+    if (int e = h->body_maps.upload(o_tab, wtab, tab_bytes, h->stream)) return e;
+    if (int e = p.clear(base, h->stream)) return e;
+    const WindowArgs *dw = (const WindowArgs *)(base + o_tab);
+    const BodyMapArgs *da = (const BodyMapArgs *)(dw + n);
     // ---- insert, pixels, flag, scan
     const dim3 pixel_grid((unsigned)n_blocks, (unsigned)n), surfel_grid((unsigned)((max_count + SFP_BLOCK - 1) / SFP_BLOCK), (unsigned)n);
     if (max_count) hipLaunchKernelGGL(sfp_insert_kernel, surfel_grid, dim3(SFP_BLOCK), 0, h->stream, da);
     hipLaunchKernelGGL(sfp_pixel_kernel, pixel_grid, dim3(SFP_BLOCK), 0, h->stream, da, rows, cols);
     hipLaunchKernelGGL(sfp_flag_kernel, pixel_grid, dim3(SFP_BLOCK), 0, h->stream, da, rows, cols);
-    hipLaunchKernelGGL(sfp_window::sfw_scan_kernel, dim3((unsigned)n), dim3(1024), 0, h->stream, dw);
+    sfw_launch_scan(h, dw, n);
     HIP_TRY(hipGetLastError());
     std::vector<int> res((size_t)n * SFP_COUNT_WORDS, 0);
     if (int e = d2h(h, res.data(), base + o_counts, res.size() * sizeof(int))) return e;
@@ -240,7 +211,7 @@ int sfp_check_params(const sfp_params *p) { return check_params(p); }
 int sfp_pixel_surfel(const float depths[5], int v, int u, const sfp_camera *cam, const uint8_t *colour, const sfp_params *p, float time, float out[12]) {
     if (!depths || !cam || !out) return fail(SF_ERR_ARG, "sfp_pixel_surfel: null argument");
     if (int e = check_params(p)) return e;
-    if (int e = check_camera(cam)) return e;
+    if (int e = check_camera("sfp", cam)) return e;
     const int r = colour ? colour[0] : 128, g = colour ? colour[1] : 128, b = colour ? colour[2] : 128;
     float s[12];
     if (!sfp_pixel_surfel_core(depths, v, u, cam->pose, cam->cx, cam->cy, cam->fx, cam->fy, r, g, b, p->z_max, p->normal_dz, p->conf_new, time, s)) return 0;
@@ -260,14 +231,13 @@ int sfp_move_maps(sf_handle *h, int n, sf_map *const *maps, const float *W) {
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
     if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
+    if (int e = check_batch(w, n)) return e;
     if (!maps) return fail(SF_ERR_ARG, w + ": null argument");
     if (int e = check_maps(w, h, n, maps, W)) return e;
     HIP_TRY(hipSetDevice(h->device));
     const size_t tab_bytes = (size_t)n * sizeof(BodyMapArgs);
-    if (int e = dev_grow(h, &h->body_maps_scratch, &h->body_maps_bytes, tab_bytes)) return e;
-    h->body_maps_args_host.assign(tab_bytes, 0);
-    BodyMapArgs *atab = (BodyMapArgs *)h->body_maps_args_host.data();
+    if (int e = h->body_maps.grow(h->own, tab_bytes, h->stream)) return e;
+    BodyMapArgs *atab = h->body_maps.zeroed<BodyMapArgs>((size_t)n);
     int max_count = 0;
     for (int q = 0; q < n; q++) {
         atab[(size_t)q].map = maps[q]->buf[0];
@@ -275,10 +245,10 @@ int sfp_move_maps(sf_handle *h, int n, sf_map *const *maps, const float *W) {
         set_motion(atab[(size_t)q], W, q);
         max_count = std::max(max_count, maps[q]->count);
     }
-    HIP_TRY(hipMemcpyAsync(h->body_maps_scratch, atab, tab_bytes, hipMemcpyHostToDevice, h->stream));
+    if (int e = h->body_maps.upload(0, atab, tab_bytes, h->stream)) return e;
     if (max_count)
         hipLaunchKernelGGL(sfp_move_kernel<false>, dim3((unsigned)((max_count + SFP_BLOCK - 1) / SFP_BLOCK), (unsigned)n), dim3(SFP_BLOCK), 0, h->stream,
-                           (const BodyMapArgs *)h->body_maps_scratch, 0, 0);
+                           (const BodyMapArgs *)h->body_maps.dev, 0, 0);
     HIP_TRY(hipGetLastError());
     for (int q = 0; q < n; q++) indices_moved(maps[q]);
     return SF_OK;

@@ -1,8 +1,8 @@
 // sf_hip_join.hip — libsf_hip.so, the interface of include/sf_join.h (symbols sfj_*): maps thinned to one surfel per voxel and
 // maps merged without storing a surface twice, many per call (kernels: sf_join.h; key, rank and hash: sf_join_key.h). The
-// voxel tables, the remembered slots, the ballots, the block counts, the counters and the two entry tables of a call lie in a
-// block of the join calls' own (sf_handle::join_scratch, grown when a call needs more and freed with the handle), so a call
-// leaves the scratch of every other part alone. A thin partitions a map into its idle second buffer like a cull; a merge
+// voxel tables, the remembered slots, the ballots, the block counts, the counters and the two entry tables of a call lie in
+// the call block sf_handle::join (sf_call_block.h: layout, growth and lifetime). A thin partitions a map into its idle second
+// buffer like a cull, with the scan and the ordered write of the bounded maps (sfw_launch_scan / sfw_launch_write); a merge
 // writes behind the destination's own surfels. One host synchronisation reads the counts; for a merge it lies before the
 // move, because the capacity test needs them.
 #include "../../include/sf_join.h"
@@ -23,16 +23,6 @@ static int check_params(const sfj_params *p) {
     return SF_OK;
 }
 
-// where the parts of a call lie in the block
-struct JoinPlan {
-    size_t off = 0;
-    size_t take(size_t bytes) {  // 256-byte aligned
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 struct JoinEntry {
     const sf_map *fill;  // fills the table: the map (thin), the destination (merge)
     const sf_map *src;   // examined: the map (thin), the source (merge)
@@ -46,10 +36,10 @@ static int run(sf_handle *h, bool thin, int n, const JoinEntry *entries, const s
                const WindowArgs **d_wtab, const JoinArgs **d_jtab, int *max_count_out) {
     HIP_TRY(hipSetDevice(h->device));
     // ---- layout: the two tables; what is cleared to 0 (counters, bids); what is cleared to ~0 (keys); the rest
-    JoinPlan p;
+    SfPlan p;
     const size_t tab_bytes = (size_t)n * (sizeof(WindowArgs) + sizeof(JoinArgs));
     const size_t o_tab = p.take(tab_bytes);
-    const size_t o_zero = p.off;
+    p.zeros_from_here();
     const size_t o_counts = p.take((size_t)n * SFJ_COUNT_WORDS * sizeof(int));
     std::vector<size_t> o_best((size_t)n), o_keys((size_t)n), o_slot((size_t)n), o_ballots((size_t)n), o_blocks((size_t)n);
     std::vector<int> slots((size_t)n);
@@ -57,9 +47,9 @@ static int run(sf_handle *h, bool thin, int n, const JoinEntry *entries, const s
         slots[(size_t)q] = sfj_slots_for(entries[q].fill->count);
         if (thin) o_best[(size_t)q] = p.take((size_t)slots[(size_t)q] * 8);
     }
-    const size_t o_ones = p.off;
+    p.ones_from_here();
     for (int q = 0; q < n; q++) o_keys[(size_t)q] = p.take((size_t)slots[(size_t)q] * 8);
-    const size_t o_rest = p.off;
+    p.rest_from_here();
     int max_fill = 0, max_count = 0;
     for (int q = 0; q < n; q++) {
         const size_t count = (size_t)entries[q].src->count;
@@ -69,12 +59,11 @@ static int run(sf_handle *h, bool thin, int n, const JoinEntry *entries, const s
         max_fill = std::max(max_fill, entries[q].fill->count);
         max_count = std::max(max_count, entries[q].src->count);
     }
-    if (int e = dev_grow(h, &h->join_scratch, &h->join_bytes, p.off)) return e;
-    unsigned char *base = h->join_scratch;
-    // ---- the tables (a member holds the host copy: it outlives the asynchronous upload)
-    h->join_args_host.assign(tab_bytes, 0);
-    WindowArgs *wtab = (WindowArgs *)h->join_args_host.data();
-    JoinArgs *jtab = (JoinArgs *)(h->join_args_host.data() + (size_t)n * sizeof(WindowArgs));
+    if (int e = h->join.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->join.dev;
+    // ---- the tables, zeroed: one upload
+    WindowArgs *wtab = (WindowArgs *)h->join.zeroed<unsigned char>(tab_bytes);
+    JoinArgs *jtab = (JoinArgs *)(wtab + n);
     for (int q = 0; q < n; q++) {
         const JoinEntry &en = entries[q];
         JoinArgs &a = jtab[(size_t)q];
@@ -105,11 +94,10 @@ static int run(sf_handle *h, bool thin, int n, const JoinEntry *entries, const s
         w.block_counts = a.block_counts;
         w.result = a.counts + SFJ_N_OUT;
     }
-    HIP_TRY(hipMemcpyAsync(base + o_tab, h->join_args_host.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(base + o_zero, 0, o_ones - o_zero, h->stream));
-    HIP_TRY(hipMemsetAsync(base + o_ones, 0xFF, o_rest - o_ones, h->stream));
+    if (int e = h->join.upload(o_tab, wtab, tab_bytes, h->stream)) return e;
+    if (int e = p.clear(base, h->stream)) return e;
     const WindowArgs *dw = (const WindowArgs *)(base + o_tab);
-    const JoinArgs *dj = (const JoinArgs *)(base + o_tab + (size_t)n * sizeof(WindowArgs));
+    const JoinArgs *dj = (const JoinArgs *)(dw + n);
     // ---- insert, flag, scan (and the thin's write)
     const auto grid = [n](int count) { return dim3((unsigned)((count + SFJ_BLOCK - 1) / SFJ_BLOCK), (unsigned)n); };
     if (max_fill) {
@@ -124,8 +112,8 @@ static int run(sf_handle *h, bool thin, int n, const JoinEntry *entries, const s
         else
             hipLaunchKernelGGL(sfj_merge_flag_kernel, grid(max_count), dim3(SFJ_BLOCK), 0, h->stream, dj);
     }
-    hipLaunchKernelGGL(sfj_window::sfw_scan_kernel, dim3((unsigned)n), dim3(1024), 0, h->stream, dw);
-    if (write_thin && max_count) hipLaunchKernelGGL(sfj_window::sfw_write_kernel<false>, grid(max_count), dim3(SFJ_BLOCK), 0, h->stream, dw);
+    sfw_launch_scan(h, dw, n);
+    if (write_thin && max_count) sfw_launch_write(h, dw, grid(max_count).x, n);
     HIP_TRY(hipGetLastError());
     res.assign((size_t)n * SFJ_COUNT_WORDS, 0);
     if (int e = d2h(h, res.data(), base + o_counts, res.size() * sizeof(int))) return e;
@@ -149,12 +137,6 @@ static sfj_counts counts_of(const int *r, int n_in) {
     c.n_shared = r[SFJ_N_SHARED];
     c.n_out = r[SFJ_N_OUT];
     return c;
-}
-
-// the rule AFTER A CALL THAT CHANGES A MAP of include/sf_map_window.h: surfel indices have moved
-static void indices_moved(sf_map *m, int count) {
-    m->count = count;
-    m->have_index = false;  // the index image of the last fuse no longer describes the map
 }
 
 extern "C" {
@@ -191,13 +173,12 @@ int sfj_hash_slot(uint64_t key, int slots) {
 int sfj_thin_maps(sf_handle *h, int n, sf_map *const *maps, const sfj_params *params, sfj_counts *counts_out) {
     if (!h || n < 0 || (n && (!maps || !params || !counts_out))) return fail(SF_ERR_ARG, "sfj_thin_maps: bad argument");
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, "sfj_thin_maps: more than 65535 entries in one call");
+    if (int e = check_batch("sfj_thin_maps", n)) return e;
     std::vector<JoinEntry> entries((size_t)n);
     bool any_write = false;
     for (int q = 0; q < n; q++) {
         if (int e = check_map("sfj_thin_maps", h, maps[q])) return e;
-        for (int r = 0; r < q; r++)
-            if (maps[r] == maps[q]) return fail(SF_ERR_ARG, "sfj_thin_maps: the same map twice in one batch");
+        if (int e = check_distinct("sfj_thin_maps", maps, q, "the same map twice in one batch")) return e;
         if (int e = check_params(params + q)) return e;
         entries[(size_t)q] = JoinEntry{maps[q], maps[q], nullptr};
         any_write = any_write || !params[q].dry_run;
@@ -209,7 +190,8 @@ int sfj_thin_maps(sf_handle *h, int n, sf_map *const *maps, const sfj_params *pa
         counts_out[q] = counts_of(r, maps[q]->count);
         if (params[q].dry_run) continue;
         std::swap(maps[q]->buf[0], maps[q]->buf[1]);  // the partitioned buffer becomes the map: its first n_out surfels
-        indices_moved(maps[q], r[SFJ_N_OUT]);
+        maps[q]->count = r[SFJ_N_OUT];
+        indices_moved(maps[q]);
     }
     return SF_OK;
 }
@@ -228,7 +210,7 @@ int sfj_thin_extract(sf_map *m, const sfj_params *p, float *surfels_out, int max
     const int k = res[SFJ_N_OUT];
     if (k > max_count) return fail(SF_ERR_ARG, "sfj_thin_extract: " + std::to_string(k) + " surfels, room for " + std::to_string(max_count));
     if (k == 0) return SF_OK;
-    hipLaunchKernelGGL(sfj_window::sfw_write_kernel<false>, dim3((unsigned)((max_n + SFJ_BLOCK - 1) / SFJ_BLOCK), 1u), dim3(SFJ_BLOCK), 0, h->stream, dw);
+    sfw_launch_write(h, dw, (unsigned)((max_n + SFJ_BLOCK - 1) / SFJ_BLOCK), 1);
     HIP_TRY(hipGetLastError());
     return d2h(h, surfels_out, m->buf[1], (size_t)k * 12 * sizeof(float));
 }
@@ -236,18 +218,15 @@ int sfj_thin_extract(sf_map *m, const sfj_params *p, float *surfels_out, int max
 int sfj_merge_maps(sf_handle *h, int n, sf_map *const *dst, sf_map *const *src, const float *T, const sfj_params *params, sfj_counts *counts_out) {
     if (!h || n < 0 || (n && (!dst || !src || !params || !counts_out))) return fail(SF_ERR_ARG, "sfj_merge_maps: bad argument");
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, "sfj_merge_maps: more than 65535 entries in one call");
+    if (int e = check_batch("sfj_merge_maps", n)) return e;
     std::vector<JoinEntry> entries((size_t)n);
     bool any_move = false;
     for (int q = 0; q < n; q++) {
         if (int e = check_map("sfj_merge_maps", h, dst[q])) return e;
         if (int e = check_map("sfj_merge_maps", h, src[q])) return e;
-        for (int r = 0; r < q; r++)
-            if (dst[r] == dst[q]) return fail(SF_ERR_ARG, "sfj_merge_maps: the same destination twice in one batch");
+        if (int e = check_distinct("sfj_merge_maps", dst, q, "the same destination twice in one batch")) return e;
         if (int e = check_params(params + q)) return e;
-        if (T)
-            for (int k = 0; k < 16; k++)
-                if (!std::isfinite(T[(size_t)q * 16 + k])) return fail(SF_ERR_ARG, "sfj_merge_maps: NaN or inf in T");
+        if (T && !finite_all(T + (size_t)q * 16, 16)) return fail(SF_ERR_ARG, "sfj_merge_maps: NaN or inf in T");
         entries[(size_t)q] = JoinEntry{dst[q], src[q], T ? T + (size_t)q * 16 : nullptr};
         any_move = any_move || !params[q].dry_run;
     }
@@ -268,7 +247,7 @@ int sfj_merge_maps(sf_handle *h, int n, sf_map *const *dst, sf_map *const *src, 
     if (!any_move || !max_n) return SF_OK;
     // The move of the entries that are no dry run: their tables go up again with the others' counts set to 0, behind the scan
     // that read them (one stream).
-    JoinArgs *jtab = (JoinArgs *)(h->join_args_host.data() + (size_t)n * sizeof(WindowArgs));
+    JoinArgs *jtab = (JoinArgs *)(h->join.host[0].data() + (size_t)n * sizeof(WindowArgs));
     bool changed = false;
     for (int q = 0; q < n; q++)
         if (params[q].dry_run && jtab[(size_t)q].count) {
@@ -279,7 +258,10 @@ int sfj_merge_maps(sf_handle *h, int n, sf_map *const *dst, sf_map *const *src, 
     hipLaunchKernelGGL(sfj_merge_move_kernel, dim3((unsigned)((max_n + SFJ_BLOCK - 1) / SFJ_BLOCK), (unsigned)n), dim3(SFJ_BLOCK), 0, h->stream, dj);
     HIP_TRY(hipGetLastError());
     for (int q = 0; q < n; q++)
-        if (!params[q].dry_run && res[(size_t)q * SFJ_COUNT_WORDS + SFJ_N_OUT]) indices_moved(dst[q], dst[q]->count + res[(size_t)q * SFJ_COUNT_WORDS + SFJ_N_OUT]);
+        if (!params[q].dry_run && res[(size_t)q * SFJ_COUNT_WORDS + SFJ_N_OUT]) {
+            dst[q]->count += res[(size_t)q * SFJ_COUNT_WORDS + SFJ_N_OUT];
+            indices_moved(dst[q]);
+        }
     return SF_OK;
 }
 

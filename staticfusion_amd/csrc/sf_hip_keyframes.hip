@@ -1,7 +1,7 @@
 // sf_hip_keyframes.hip — libsf_hip.so, the interface of include/sf_keyframes.h (symbols sfk_*): fern codes of frames, a
 // database of coded keyframes with their poses, the search of it and the adding to it (kernels: sf_keyframes.h). A database
-// owns its device blocks (ferns, codes, tags, a scratch block grown when a call needs more) through an owner of its own, as
-// a map does; its handle's sf_destroy releases them and leaves an empty shell. Poses and stamps, which no kernel reads, are
+// owns its device blocks (ferns, codes, tags, and the call block sfk_db::scratch: sf_call_block.h) through an owner of its
+// own, as a map does; its handle's sf_destroy releases them and leaves an empty shell. Poses and stamps, which no kernel reads, are
 // host vectors. Every call checks everything before it launches or writes anything.
 #include "../../include/sf_keyframes.h"
 #include "sf_host.h"
@@ -20,9 +20,7 @@ struct sfk_db {
     int32_t *d_tags = nullptr;    // [capacity]
     std::vector<float> poses;     // [count][16]
     std::vector<int32_t> stamps;  // [count]
-    unsigned char *scratch = nullptr;  // what one call uploads, encodes and reads back
-    size_t scratch_bytes = 0;
-    std::vector<KfFrame> frames_host;  // the host copy of a call's frame table (a member: it outlives an asynchronous call)
+    SfCallBlock scratch;          // what one call uploads, encodes and reads back; host copy 0: the frame table
     SfOwner own;
 };
 
@@ -42,14 +40,6 @@ static int check_db(const char *what, const sfk_db *db) {
     return SF_OK;
 }
 
-// n entries of a call: SF_OK with *empty set for n == 0
-static int check_count(const char *what, int n, bool *empty) {
-    *empty = n == 0;
-    if (n < 0) return fail(SF_ERR_ARG, std::string(what) + ": n < 0");
-    if (n > 65535) return fail(SF_ERR_ARG, std::string(what) + ": more than 65535 entries in one call");
-    return SF_OK;
-}
-
 static int check_streams(const char *what, const sfk_db *db, int n, const int32_t *streams) {
     const sf_handle *h = db->h;
     if (db->rows != h->k.rows || db->cols != h->k.cols) return fail(SF_ERR_ARG, std::string(what) + ": a database of another size than the handle's streams");
@@ -58,35 +48,24 @@ static int check_streams(const char *what, const sfk_db *db, int n, const int32_
     return SF_OK;
 }
 
-// ---- the layout of a call's scratch block (256-byte aligned pieces) and the launches ----------------------------------
-struct KfPlan {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
-static int grow_scratch(sfk_db *db, size_t bytes) { return db->own.grow(&db->scratch, &db->scratch_bytes, bytes, db->h->stream); }
-
-enum EncodeForm { FORM_STREAMS, FORM_HOST, FORM_DEVICE };
+// ---- a call's scratch block (under the database's own owner) and the launches ------------------------------------------
+static int grow_scratch(sfk_db *db, size_t bytes) { return db->scratch.grow(db->own, bytes, db->h->stream); }
 
 // frames -> codes [n][words] at d_codes, on the handle's stream. The frame table lies at o_frames of the scratch block; the
 // host images of FORM_HOST are uploaded to o_images (n x 2 images). Everything has been checked and the block has been grown.
-static int encode(sfk_db *db, EncodeForm form, int n, const int32_t *streams, const void *const *depth, const void *const *grey, size_t o_frames,
+static int encode(sfk_db *db, CallForm form, int n, const int32_t *streams, const void *const *depth, const void *const *grey, size_t o_frames,
                   size_t o_images, uint32_t *d_codes) {
     sf_handle *h = db->h;
     const size_t px = (size_t)db->rows * db->cols;
-    db->frames_host.resize((size_t)n);
+    KfFrame *frames = db->scratch.resized<KfFrame>((size_t)n);
     uintptr_t bits = 0;  // the alignment of every image of the call
     for (int q = 0; q < n; q++) {
-        KfFrame &f = db->frames_host[(size_t)q];
+        KfFrame &f = frames[(size_t)q];
         if (form == FORM_STREAMS) {
             f.depth = h->k.pyr_new[0] + (size_t)streams[q] * h->k.n_tot;  // what sf_get_current copies out and sfs_score_streams reads
             f.grey = h->k.pyr_new[1] + (size_t)streams[q] * h->k.n_tot;
         } else if (form == FORM_HOST) {
-            float *d = (float *)(db->scratch + o_images) + (size_t)q * 2 * px;
+            float *d = (float *)(db->scratch.dev + o_images) + (size_t)q * 2 * px;
             HIP_TRY(hipMemcpyAsync(d, depth[q], px * 4, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(hipMemcpyAsync(d + px, grey[q], px * 4, hipMemcpyHostToDevice, h->stream));
             f.depth = d;
@@ -97,8 +76,8 @@ static int encode(sfk_db *db, EncodeForm form, int n, const int32_t *streams, co
         }
         bits |= (uintptr_t)f.depth | (uintptr_t)f.grey;
     }
-    KfFrame *d_frames = (KfFrame *)(db->scratch + o_frames);
-    HIP_TRY(hipMemcpyAsync(d_frames, db->frames_host.data(), (size_t)n * sizeof(KfFrame), hipMemcpyHostToDevice, h->stream));
+    KfFrame *d_frames = (KfFrame *)(db->scratch.dev + o_frames);
+    if (int e = db->scratch.upload(o_frames, frames, (size_t)n * sizeof(KfFrame), h->stream)) return e;
     // the widest load: W floats that never straddle a cell, start on a multiple of W in every column, and are aligned
     int w = 1;
     if (db->cell % 4 == 0 && db->rows % 4 == 0 && bits % 16 == 0) w = 4;
@@ -121,12 +100,11 @@ static int search(sfk_db *db, int n, const uint32_t *d_codes, const int32_t *d_t
     return SF_OK;
 }
 
-static int encode_to_host(const char *what, EncodeForm form, sfk_db *db, int n, const int32_t *streams, const float *const *depth, const float *const *grey,
+static int encode_to_host(const char *what, CallForm form, sfk_db *db, int n, const int32_t *streams, const float *const *depth, const float *const *grey,
                           uint32_t *codes_out) {
     if (int e = check_db(what, db)) return e;
-    bool empty;
-    if (int e = check_count(what, n, &empty)) return e;
-    if (empty) return SF_OK;
+    if (int e = check_batch(what, n)) return e;
+    if (n == 0) return SF_OK;
     if (!codes_out || (form == FORM_STREAMS ? !streams : (!depth || !grey))) return fail(SF_ERR_ARG, std::string(what) + ": null argument");
     if (form == FORM_STREAMS) {
         if (int e = check_streams(what, db, n, streams)) return e;
@@ -136,12 +114,12 @@ static int encode_to_host(const char *what, EncodeForm form, sfk_db *db, int n, 
     }
     sf_handle *h = db->h;
     HIP_TRY(hipSetDevice(h->device));
-    KfPlan p;
+    SfPlan p;
     const size_t o_frames = p.take((size_t)n * sizeof(KfFrame));
     const size_t o_codes = p.take((size_t)n * db->words * 4);
     const size_t o_images = form == FORM_HOST ? p.take((size_t)n * 2 * db->rows * db->cols * 4) : 0;
     if (int e = grow_scratch(db, p.off)) return e;
-    uint32_t *d_codes = (uint32_t *)(db->scratch + o_codes);
+    uint32_t *d_codes = (uint32_t *)(db->scratch.dev + o_codes);
     if (int e = encode(db, form, n, streams, (const void *const *)depth, (const void *const *)grey, o_frames, o_images, d_codes)) return e;
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(codes_out, d_codes, (size_t)n * db->words * 4, hipMemcpyDeviceToHost));
@@ -161,9 +139,8 @@ static int check_tags(const char *what, int n, const int32_t *tags) {  // of an 
 static int query_or_add(const char *what, sfk_db *db, int n, const int32_t *streams, const uint32_t *codes, bool from_streams, const int32_t *tags, int m,
                         sfk_match *matches_out, bool add, const float *poses, const int32_t *stamps, int min_distance, int32_t *slots_out) {
     if (int e = check_db(what, db)) return e;
-    bool empty;
-    if (int e = check_count(what, n, &empty)) return e;
-    if (empty) return SF_OK;
+    if (int e = check_batch(what, n)) return e;
+    if (n == 0) return SF_OK;
     if (!tags || (from_streams ? !streams : !codes)) return fail(SF_ERR_ARG, std::string(what) + ": null argument");
     if (add) {
         if (!poses || !stamps || !slots_out) return fail(SF_ERR_ARG, std::string(what) + ": null argument");
@@ -178,16 +155,16 @@ static int query_or_add(const char *what, sfk_db *db, int n, const int32_t *stre
     sf_handle *h = db->h;
     HIP_TRY(hipSetDevice(h->device));
     const size_t code_bytes = (size_t)n * db->words * 4;
-    KfPlan p;
+    SfPlan p;
     const size_t o_frames = p.take((size_t)n * sizeof(KfFrame));
     const size_t o_codes = p.take(code_bytes);
     const size_t o_tags = p.take((size_t)n * 4);
     const size_t o_match = p.take((size_t)n * m * sizeof(sfk_match));
     const size_t o_slots = p.take((size_t)n * 4);
     if (int e = grow_scratch(db, p.off)) return e;
-    uint32_t *d_codes = (uint32_t *)(db->scratch + o_codes);
-    int32_t *d_tags = (int32_t *)(db->scratch + o_tags), *d_slots = (int32_t *)(db->scratch + o_slots);
-    sfk_match *d_match = (sfk_match *)(db->scratch + o_match);
+    uint32_t *d_codes = (uint32_t *)(db->scratch.dev + o_codes);
+    int32_t *d_tags = (int32_t *)(db->scratch.dev + o_tags), *d_slots = (int32_t *)(db->scratch.dev + o_slots);
+    sfk_match *d_match = (sfk_match *)(db->scratch.dev + o_match);
     if (from_streams) {
         if (int e = encode(db, FORM_STREAMS, n, streams, nullptr, nullptr, o_frames, 0, d_codes)) return e;
     } else {
@@ -371,14 +348,13 @@ int sfk_encode_images(sfk_db *db, int n, const float *const *depth, const float 
 int sfk_encode_images_device(sfk_db *db, int n, const void *const *depth, const void *const *grey, void *d_codes) {
     const char *what = "sfk_encode_images_device";
     if (int e = check_db(what, db)) return e;
-    bool empty;
-    if (int e = check_count(what, n, &empty)) return e;
-    if (empty) return SF_OK;
+    if (int e = check_batch(what, n)) return e;
+    if (n == 0) return SF_OK;
     if (!depth || !grey || !d_codes) return fail(SF_ERR_ARG, std::string(what) + ": null argument");
     for (int q = 0; q < n; q++)
         if (!depth[q] || !grey[q]) return fail(SF_ERR_ARG, std::string(what) + ": null image");
     HIP_TRY(hipSetDevice(db->h->device));
-    KfPlan p;
+    SfPlan p;
     const size_t o_frames = p.take((size_t)n * sizeof(KfFrame));
     if (int e = grow_scratch(db, p.off)) return e;
     return encode(db, FORM_DEVICE, n, nullptr, depth, grey, o_frames, 0, (uint32_t *)d_codes);

@@ -2,7 +2,8 @@
 // budget by a stable partition of its surfel buffer into its idle second buffer (kernels: sf_map_window.h). Cull swaps the
 // two buffers afterwards, extract copies the front part out, page-out copies the back part out and swaps. No frame kernel
 // and no kernel of the fusion is involved; the scratch is the map's own clean-stage scratch (flags, block_counts), idle
-// between two fuses.
+// between two fuses. The join and the body maps launch the scan and the ordered write from here (sfw_launch_scan,
+// sfw_launch_write), so the library holds those kernels once.
 #include "../../include/sf_map_window.h"
 #include "sf_host.h"
 #include "sf_map_window.h"
@@ -32,8 +33,7 @@ static int check_filter(const sfw_filter *f) {
 static int check_maps(const char *what, sf_handle *h, int n, sf_map *const *maps, const sfw_filter *filters) {
     for (int q = 0; q < n; q++) {
         if (int e = check_map(what, h, maps[q])) return e;
-        for (int r = 0; r < q; r++)
-            if (maps[r] == maps[q]) return fail(SF_ERR_ARG, std::string(what) + ": the same map twice in one batch");
+        if (int e = check_distinct(what, maps, q, "the same map twice in one batch")) return e;
         if (int e = check_filter(filters + q)) return e;
         if (((size_t)maps[q]->count + 63) / 64 * 8 > (size_t)maps[q]->capacity) return fail(SF_ERR_STATE, std::string(what) + ": map too small for its own scratch");
     }
@@ -47,6 +47,14 @@ static void launch_write(sf_handle *h, const WindowArgs *tab, int n, int max_cou
         hipLaunchKernelGGL(sfw_write_kernel<true>, grid, dim3(SFW_BLOCK), 0, h->stream, tab);
     else
         hipLaunchKernelGGL(sfw_write_kernel<false>, grid, dim3(SFW_BLOCK), 0, h->stream, tab);
+}
+
+// ---- the scan and the ordered write for the join and the body maps (declared in sf_host.h)
+void sfw_launch_scan(sf_handle *h, const WindowArgs *d_tab, int n) {
+    hipLaunchKernelGGL(sfw_scan_kernel, dim3((unsigned)n), dim3(1024), 0, h->stream, d_tab);
+}
+void sfw_launch_write(sf_handle *h, const WindowArgs *d_tab, unsigned blocks, int n) {
+    hipLaunchKernelGGL(sfw_write_kernel<false>, dim3(blocks, (unsigned)n), dim3(SFW_BLOCK), 0, h->stream, d_tab);
 }
 
 // Predicate pass and scan for n checked maps of h (with `write`: the move into buf[1] as well; move_rest: the surfels not
@@ -90,7 +98,7 @@ static int partition(sf_handle *h, int n, sf_map *const *maps, const sfw_filter 
         else
             hipLaunchKernelGGL(sfw_flag_kernel<false>, grid, dim3(SFW_BLOCK), 0, h->stream, dev);
     }
-    hipLaunchKernelGGL(sfw_scan_kernel, dim3((unsigned)n), dim3(1024), 0, h->stream, dev);
+    sfw_launch_scan(h, dev, n);
     if (write) launch_write(h, dev, n, max_count);
     HIP_TRY(hipGetLastError());
     std::vector<int> res((size_t)n * 8);
@@ -108,7 +116,7 @@ static int partition(sf_handle *h, int n, sf_map *const *maps, const sfw_filter 
 static void adopt(sf_map *m, int k) {
     std::swap(m->buf[0], m->buf[1]);
     m->count = k;
-    m->have_index = false;  // surfel indices have moved: the index image of the last fuse no longer describes the map
+    indices_moved(m);
 }
 
 extern "C" {
@@ -174,7 +182,7 @@ int sfw_append(sf_map *m, const float *surfels, int count) {
         HIP_TRY(hipStreamSynchronize(m->h->stream));  // the host buffer is free again
     }
     m->count += count;
-    m->have_index = false;
+    indices_moved(m);
     return SF_OK;
 }
 

@@ -1,8 +1,8 @@
 // sf_hip_regions.hip — libsf_hip.so, the interface of include/sf_regions.h (symbols sfr_*): connected components of the moving
 // pixels of many frames per call, numbered, with one integer record per region (kernels: sf_regions.h). A call's scratch --
 // the entry table, the provisional label image and the count image of every entry, the block counts of the numbering and,
-// for the host forms, the uploaded frames, the records and the label images -- is one block of the handle
-// (sf_handle::regions_scratch), grown when a call needs more and freed with the handle. A call only reads its streams.
+// for the host forms, the uploaded frames, the records and the label images -- is the call block sf_handle::regions
+// (sf_call_block.h: layout, growth and lifetime). A call only reads its streams.
 #include "../../include/sf_regions.h"
 #include "sf_host.h"
 #include "sf_regions.h"
@@ -13,10 +13,10 @@ static_assert(sizeof(sfr_region) == 64, "include/sf_regions.h: sfr_region is 64 
 static_assert(sizeof(sfr_summary) == 32, "include/sf_regions.h: sfr_summary is 32 bytes");
 static_assert(SFR_NB == 4 * SFR_NT && SFR_TV == 64 && (SFR_TV * SFR_TU) % SFR_NT == 0 && SFR_RUN == 8, "sf_regions.h: the lanes' shares");
 
+static_assert(offsetof(sfr_params, dz_rel) == 12, "the four floats of sfr_params are consecutive");
 static int check_params(const sfr_params *p) {
     if (!p) return fail(SF_ERR_ARG, "sfr: null params");
-    if (!(std::isfinite(p->z_max) && std::isfinite(p->b_max) && std::isfinite(p->dz_abs) && std::isfinite(p->dz_rel)))
-        return fail(SF_ERR_ARG, "sfr: NaN or inf in sfr_params");
+    if (!finite_all(&p->z_max, 4)) return fail(SF_ERR_ARG, "sfr: NaN or inf in sfr_params");
     if (!(p->z_max > 0.f && p->z_max <= 32.f)) return fail(SF_ERR_ARG, "sfr: z_max lies in (0, 32]");
     if (p->dz_abs < 0.f || p->dz_rel < 0.f) return fail(SF_ERR_ARG, "sfr: a negative dz_abs or dz_rel");
     if (p->connectivity != 4 && p->connectivity != 8) return fail(SF_ERR_ARG, "sfr: connectivity is 4 or 8");
@@ -25,33 +25,21 @@ static int check_params(const sfr_params *p) {
     return SF_OK;
 }
 
-enum RegionForm { FORM_STREAMS, FORM_HOST, FORM_DEVICE };
-
-struct RgPlan {
-    size_t off = 0;
-    size_t take(size_t bytes) {  // 256-byte aligned
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 // every check of the refusal list, then: grow, upload, the seven launches, and for the host forms the copies back
-static int label(const char *what, RegionForm form, sf_handle *h, int rows, int cols, int n, const int32_t *streams, const void *const *depth,
+static int label(const char *what, CallForm form, sf_handle *h, int rows, int cols, int n, const int32_t *streams, const void *const *depth,
                  const void *const *b, const sfr_params *params, int max_regions, void *summaries, void *regions, void *const *labels) {
     const std::string w(what);
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
     if (n == 0) return SF_OK;
     if (!params || !summaries || (form == FORM_STREAMS ? !streams : !depth)) return fail(SF_ERR_ARG, w + ": null argument");
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
+    if (int e = check_batch(w, n)) return e;
     if (max_regions < 0 || max_regions > 65535) return fail(SF_ERR_ARG, w + ": max_regions lies in 0..65535");
     if (max_regions > 0 && !regions) return fail(SF_ERR_ARG, w + ": null regions_out with max_regions > 0");
     if (form == FORM_STREAMS) {
         rows = h->k.rows;
         cols = h->k.cols;
     }
-    if (rows < 1 || rows > 4096 || cols < 1 || cols > 4096 || (long long)rows * cols > (1ll << 24))
-        return fail(SF_ERR_ARG, w + ": rows and cols lie in 1..4096 and rows * cols <= 2^24");
+    if (int e = check_image_size(w, rows, cols)) return e;
     for (int q = 0; q < n; q++) {
         if (int e = check_params(params + q)) return e;
         if (form == FORM_STREAMS) {
@@ -65,7 +53,7 @@ static int label(const char *what, RegionForm form, sf_handle *h, int rows, int 
     // ---- layout
     const RgGeom g = rg_geometry(rows, cols);
     const size_t px = (size_t)g.px;
-    RgPlan p;
+    SfPlan p;
     const size_t o_args = p.take((size_t)n * sizeof(RgArgs));
     const size_t o_prov = p.take((size_t)n * g.pxs * 4);
     const size_t o_cnt = p.take((size_t)n * g.pxs * 4);
@@ -86,11 +74,10 @@ static int label(const char *what, RegionForm form, sf_handle *h, int rows, int 
             if (labels && labels[q]) o_lab[(size_t)q] = p.take(px * 4);
         }
     }
-    if (int e = dev_grow(h, &h->regions_scratch, &h->regions_bytes, p.off)) return e;
-    unsigned char *base = h->regions_scratch;
+    if (int e = h->regions.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->regions.dev;
     // ---- the entry table
-    h->regions_args_host.resize((size_t)n * sizeof(RgArgs));  // (a member: it outlives an asynchronous call)
-    RgArgs *tab = (RgArgs *)h->regions_args_host.data();
+    RgArgs *tab = h->regions.resized<RgArgs>((size_t)n);
     for (int q = 0; q < n; q++) {
         RgArgs &a = tab[(size_t)q];
         const sfr_params &sp = params[q];
@@ -116,7 +103,7 @@ static int label(const char *what, RegionForm form, sf_handle *h, int rows, int 
     int *d_prov = (int *)(base + o_prov), *d_cnt = (int *)(base + o_cnt), *d_blocks = (int *)(base + o_blocks);
     sfr_summary *d_sum = form == FORM_DEVICE ? (sfr_summary *)summaries : (sfr_summary *)(base + o_sum);
     sfr_region *d_reg = form == FORM_DEVICE ? (sfr_region *)regions : (sfr_region *)(base + o_reg);
-    HIP_TRY(hipMemcpyAsync(base + o_args, tab, (size_t)n * sizeof(RgArgs), hipMemcpyHostToDevice, h->stream));
+    if (int e = h->regions.upload(o_args, tab, (size_t)n * sizeof(RgArgs), h->stream)) return e;
     HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)n * sizeof(sfr_summary), h->stream));
     // ---- the seven launches: every grid-wide order is a launch boundary
     const unsigned un = (unsigned)n;

@@ -1,9 +1,8 @@
 // sf_hip_score.hip — libsf_hip.so, the interface of include/sf_score.h (symbols sfs_*): frame-to-map agreement counts of many
 // (map, view, frame) entries per call (kernel: sf_score.h). The maps are drawn by the drawing stage of the views
-// (sfv_plan / sfv_draw_keys of sf_hip_view.hip) into a block of the score calls' own (sf_handle::score_scratch, grown when a
-// call needs more and freed with the handle); behind the drawing layout lie the score table, the result records and -- for
-// the host-pointer calls -- the uploaded frames and the class images. A score call only reads its maps and streams and
-// leaves the view scratch, and with it sfv_last_large_sprites, alone.
+// (sfv_plan / sfv_draw_keys of sf_hip_view.hip) into the call block sf_handle::score (sf_call_block.h: layout, growth and
+// lifetime); behind the drawing layout lie the score table, the result records and -- for the host-pointer calls -- the
+// uploaded frames and the class images. A score call only reads its maps and streams.
 #include "../../include/sf_score.h"
 #include "sf_host.h"
 #include "sf_score.h"
@@ -13,27 +12,25 @@ static_assert(sizeof(sfs_params) == 32, "include/sf_score.h: sfs_params is 32 by
 static_assert(sizeof(sfs_score) == 96, "include/sf_score.h: sfs_score is 96 bytes");
 static_assert(sizeof(sfs_score) == 12 * sizeof(long long) && SFS_FIELDS == 10, "sfs_score_kernel adds the first ten int64 fields");
 
+static_assert(offsetof(sfs_params, b_min) == 12, "the four floats of sfs_params are consecutive");
 static int check_params(const sfs_params *p) {
     if (!p) return fail(SF_ERR_ARG, "sfs: null params");
-    if (!(std::isfinite(p->tol_abs) && std::isfinite(p->tol_rel) && std::isfinite(p->max_residual) && std::isfinite(p->b_min)))
-        return fail(SF_ERR_ARG, "sfs: NaN or inf in sfs_params");
+    if (!finite_all(&p->tol_abs, 4)) return fail(SF_ERR_ARG, "sfs: NaN or inf in sfs_params");
     if (p->tol_abs < 0.f || p->tol_rel < 0.f) return fail(SF_ERR_ARG, "sfs: a negative tolerance");
     if (!(p->max_residual > 0.f && p->max_residual <= 32.f)) return fail(SF_ERR_ARG, "sfs: max_residual lies in (0, 32]");
     if ((p->use_grey != 0 && p->use_grey != 1) || (p->use_b != 0 && p->use_b != 1)) return fail(SF_ERR_ARG, "sfs: use_grey and use_b are 0 or 1");
     return SF_OK;
 }
 
-enum ScoreForm { FORM_STREAMS, FORM_HOST, FORM_DEVICE };
-
 // every check of the refusal list, then: plan, grow, upload, draw, score, and for the host forms the copies back
-static int score(const char *what, ScoreForm form, sf_handle *h, int n, sf_map *const *maps, const sfv_view *views, const int32_t *streams,
+static int score(const char *what, CallForm form, sf_handle *h, int n, sf_map *const *maps, const sfv_view *views, const int32_t *streams,
                  const void *const *depth, const void *const *grey, const void *const *b, const sfs_params *params, void *scores,
                  void *const *class_out) {
     const std::string w(what);
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
     if (n == 0) return SF_OK;
     if (!maps || !views || !params || !scores || (form == FORM_STREAMS ? !streams : !depth)) return fail(SF_ERR_ARG, w + ": null argument");
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
+    if (int e = check_batch(w, n)) return e;
     std::vector<ViewJob> jobs((size_t)n);
     for (int q = 0; q < n; q++) {
         const sf_map *m = maps[q];
@@ -68,11 +65,10 @@ static int score(const char *what, ScoreForm form, sf_handle *h, int n, sf_map *
         }
         if (form != FORM_DEVICE && class_out && class_out[q]) o_cls[(size_t)q] = p.take(px);
     }
-    if (int e = dev_grow(h, &h->score_scratch, &h->score_bytes, p.off)) return e;
-    unsigned char *base = h->score_scratch;
-    // ---- the score table
-    h->score_args_host.resize((size_t)n * sizeof(ScoreArgs));  // (a member, like the view table: it outlives an asynchronous call)
-    ScoreArgs *stab = (ScoreArgs *)h->score_args_host.data();
+    if (int e = h->score.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->score.dev;
+    // ---- the score table (host copy 1; the view table is copy 0)
+    ScoreArgs *stab = h->score.resized<ScoreArgs>((size_t)n, 1);
     long long *d_rec = form == FORM_DEVICE ? (long long *)scores : (long long *)(base + o_rec);
     for (int q = 0; q < n; q++) {
         ScoreArgs &s = stab[(size_t)q];
@@ -101,10 +97,10 @@ static int score(const char *what, ScoreForm form, sf_handle *h, int n, sf_map *
         if (form == FORM_DEVICE) s.cls = class_out ? (uint8_t *)class_out[q] : nullptr;
         else s.cls = (class_out && class_out[q]) ? base + o_cls[(size_t)q] : nullptr;
     }
-    HIP_TRY(hipMemcpyAsync(base + o_stab, stab, (size_t)n * sizeof(ScoreArgs), hipMemcpyHostToDevice, h->stream));
+    if (int e = h->score.upload(o_stab, stab, (size_t)n * sizeof(ScoreArgs), h->stream)) return e;
     HIP_TRY(hipMemsetAsync(d_rec, 0, (size_t)n * sizeof(sfs_score), h->stream));
     // ---- draw the keys, then score
-    if (int e = sfv_draw_keys(h, p, jobs.data(), views, nullptr, base, h->score_tab_host, nullptr, 0)) return e;
+    if (int e = sfv_draw_keys(h, p, jobs.data(), views, nullptr, h->score, nullptr, 0)) return e;
     const unsigned per_block = SFS_NT * SFS_PER_THREAD;
     hipLaunchKernelGGL(sfs_score_kernel, dim3((unsigned)((max_px + per_block - 1) / per_block), (unsigned)n), dim3(SFS_NT), 0, h->stream,
                        (const ViewArgs *)(base + p.o_tab), (const ScoreArgs *)(base + o_stab));

@@ -1,8 +1,9 @@
 // sf_hip_tracks.hip — libsf_hip.so, the interface of include/sf_tracks.h (symbols sft_*): the moving regions of
 // include/sf_regions.h followed from frame to frame (kernels: sf_tracks.h; the assignment: sf_track_assign.h). A tracker's
 // state -- per slot the head, the camera, the rows and the previous frame's clipped labels and depth -- is one block of the
-// handle, and so is its scratch -- the entry table, the records, summaries and label images of the labelling, the overlap
-// tables and, for the host forms, the uploaded frames and the outputs of a call --, grown when a call needs more (dev_grow).
+// handle, and its scratch -- the entry table, the records, summaries and label images of the labelling, the overlap tables
+// and, for the host forms, the uploaded frames and the outputs of a call -- a call block under the handle's owner
+// (sft_tracker::scratch; sf_call_block.h: layout, growth and lifetime).
 // The labelling is sfr_label_images_device as it is: its own scratch is the handle's regions block. What the host keeps per
 // slot is what it handed in itself: whether the slot holds a previous frame, and that frame's camera.
 #include "../../include/sf_tracks.h"
@@ -22,33 +23,19 @@ struct sft_tracker {
     int rows = 0, cols = 0, n_slots = 0, max_tracks = 0;
     TkLayout lay{};
     unsigned char *state = nullptr;    // n_slots * lay.stride bytes (zero-filled: every slot is fresh)
-    unsigned char *scratch = nullptr;  // what one call uploads, computes and reads back
-    size_t scratch_bytes = 0;
-    std::vector<TkArgs> args_host;     // the host copies of a call's tables (members: they outlive an asynchronous call)
-    std::vector<int32_t> slots_host;
+    SfCallBlock scratch;               // what one call uploads, computes and reads back (host copy 0: the entry table of an
+                                       // update, host copy 1: the slots of a reset); a block of the handle's owner
     std::vector<unsigned char> has_prev;  // per slot: it holds a previous frame
     std::vector<sft_camera> cams;         // per slot: that frame's camera
 };
-
-static bool finite_all(const float *p, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
 
 static int check_track_params(const sft_params *p) {
     if (!p) return fail(SF_ERR_ARG, "sft: null params");
     if (p->min_overlap < 1) return fail(SF_ERR_ARG, "sft: min_overlap < 1");
     if (p->min_share < 0 || p->min_share > 1024) return fail(SF_ERR_ARG, "sft: min_share lies in 0..1024");
     if (p->use_depth_gate != 0 && p->use_depth_gate != 1) return fail(SF_ERR_ARG, "sft: use_depth_gate is 0 or 1");
-    if (!(std::isfinite(p->dz_abs) && std::isfinite(p->dz_rel))) return fail(SF_ERR_ARG, "sft: NaN or inf in sft_params");
+    if (!finite_all(&p->dz_abs, 2)) return fail(SF_ERR_ARG, "sft: NaN or inf in sft_params");
     if (p->dz_abs < 0.f || p->dz_rel < 0.f) return fail(SF_ERR_ARG, "sft: a negative dz_abs or dz_rel");
-    return SF_OK;
-}
-
-static int check_camera(const sft_camera *c) {
-    if (!finite_all(c->pose, 16) || !finite_all(&c->cx, 4)) return fail(SF_ERR_ARG, "sft: NaN or inf in sft_camera");
-    if (c->fx == 0.f || c->fy == 0.f) return fail(SF_ERR_ARG, "sft: fx or fy is 0");
     return SF_OK;
 }
 
@@ -82,19 +69,8 @@ static int check_tracker(const char *what, const sft_tracker *t) {
     return SF_OK;
 }
 
-enum TrackForm { FORM_STREAMS, FORM_HOST, FORM_DEVICE };
-
-struct TkPlan {
-    size_t off = 0;
-    size_t take(size_t bytes) {  // 256-byte aligned
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 static TkLayout slot_layout(int rows, int cols, int max_tracks) {
-    TkPlan p;
+    SfPlan p;
     TkLayout l;
     p.take(sizeof(TkSlotHead));
     l.o_cam = p.take(sizeof(sft_camera));
@@ -108,14 +84,13 @@ static TkLayout slot_layout(int rows, int cols, int max_tracks) {
 }
 
 // every check of the refusal list, then: grow, upload, the labelling, the three launches, and for the host forms the copies back
-static int update(const char *what, TrackForm form, sft_tracker *t, int rows, int cols, int n, const int32_t *slots, const int32_t *streams,
+static int update(const char *what, CallForm form, sft_tracker *t, int rows, int cols, int n, const int32_t *slots, const int32_t *streams,
                   const void *const *depth, const void *const *b, const sft_camera *cameras, const sfr_params *rparams, const sft_params *tparams, void *summaries,
                   void *tracks, void *const *ids) {
     const std::string w(what);
     if (int e = check_tracker(what, t)) return e;
-    if (n < 0) return fail(SF_ERR_ARG, w + ": n < 0");
+    if (int e = check_batch(w, n)) return e;
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 entries in one call");
     if (!slots || !cameras || !rparams || !tparams || !summaries || !tracks || (form == FORM_STREAMS ? !streams : !depth))
         return fail(SF_ERR_ARG, w + ": null argument");
     sf_handle *h = t->h;
@@ -133,7 +108,7 @@ static int update(const char *what, TrackForm form, sft_tracker *t, int rows, in
         seen[(size_t)slots[q]] = 1;
         if (int e = sfr_check_params(rparams + q)) return e;
         if (int e = check_track_params(tparams + q)) return e;
-        if (int e = check_camera(cameras + q)) return e;
+        if (int e = check_camera("sft", cameras + q)) return e;
         if (form == FORM_STREAMS) {
             if (int e = check_stream(h, streams[q])) return e;  // where sf_get_current / sf_get_b_image refuse, with their code
         } else {
@@ -145,7 +120,7 @@ static int update(const char *what, TrackForm form, sft_tracker *t, int rows, in
     // ---- layout
     const int M = t->max_tracks;
     const size_t px = (size_t)rows * cols;
-    TkPlan p;
+    SfPlan p;
     const size_t o_args = p.take((size_t)n * sizeof(TkArgs));
     const size_t o_rsum = p.take((size_t)n * sizeof(sfr_summary));
     const size_t o_rreg = p.take((size_t)n * M * sizeof(sfr_region));
@@ -167,8 +142,8 @@ static int update(const char *what, TrackForm form, sft_tracker *t, int rows, in
             if (ids && ids[q]) o_ids[(size_t)q] = p.take(px * 4);
         }
     }
-    if (int e = dev_grow(h, &t->scratch, &t->scratch_bytes, p.off)) return e;
-    unsigned char *base = t->scratch;
+    if (int e = t->scratch.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = t->scratch.dev;
     // ---- the frames, and the labelling as sf_regions.h has it: labels, summaries and records into the scratch
     std::vector<const void *> dp((size_t)n), bp((size_t)n);
     std::vector<void *> lp((size_t)n);
@@ -193,13 +168,12 @@ static int update(const char *what, TrackForm form, sft_tracker *t, int rows, in
     sfr_region *d_rreg = (sfr_region *)(base + o_rreg);
     if (int e = sfr_label_images_device(h, rows, cols, n, dp.data(), bp.data(), rparams, M, d_rsum, d_rreg, lp.data())) return e;
     // ---- the entry table
-    t->args_host.resize((size_t)n);
+    TkArgs *tab = t->scratch.zeroed<TkArgs>((size_t)n);
     bool any_prev = false;
     for (int q = 0; q < n; q++) {
-        TkArgs &a = t->args_host[(size_t)q];
+        TkArgs &a = tab[(size_t)q];
         const size_t s = (size_t)slots[q];
         const sft_params &tp = tparams[q];
-        std::memset(&a, 0, sizeof(a));
         a.depth = (const float *)dp[(size_t)q];
         a.labels = (const int *)lp[(size_t)q];
         if (form == FORM_DEVICE) a.ids = ids ? (int *)ids[q] : nullptr;
@@ -221,7 +195,7 @@ static int update(const char *what, TrackForm form, sft_tracker *t, int rows, in
     int *d_O = (int *)(base + o_O);
     sft_summary *d_sum = form == FORM_DEVICE ? (sft_summary *)summaries : (sft_summary *)(base + o_sum);
     sft_track *d_trk = form == FORM_DEVICE ? (sft_track *)tracks : (sft_track *)(base + o_trk);
-    HIP_TRY(hipMemcpyAsync(base + o_args, t->args_host.data(), (size_t)n * sizeof(TkArgs), hipMemcpyHostToDevice, h->stream));
+    if (int e = t->scratch.upload(o_args, tab, (size_t)n * sizeof(TkArgs), h->stream)) return e;
     HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)n * sizeof(sft_summary), h->stream));
     // ---- the three launches: every grid-wide order is a launch boundary
     const unsigned un = (unsigned)n;
@@ -251,8 +225,8 @@ static int update(const char *what, TrackForm form, sft_tracker *t, int rows, in
 // (a tracker's blocks are the handle's: sf_destroy releases them with everything else of the handle)
 void orphan_trackers(sf_handle *h) {
     for (sft_tracker *t : h->trackers) {
-        t->state = t->scratch = nullptr;
-        t->scratch_bytes = 0;
+        t->state = nullptr;
+        t->scratch.forget();
         t->h = nullptr;
     }
     h->trackers.clear();
@@ -299,8 +273,7 @@ int sft_assign(int k_prev, int k, const int32_t *overlap, const int32_t *n_prev,
 
 int sft_tracker_create(sf_handle *h, int rows, int cols, int n_slots, int max_tracks, sft_tracker **out) {
     if (!h || !out) return fail(SF_ERR_ARG, "sft_tracker_create: null argument");
-    if (rows < 1 || rows > 4096 || cols < 1 || cols > 4096 || (long long)rows * cols > (1ll << 24))
-        return fail(SF_ERR_ARG, "sft_tracker_create: rows and cols lie in 1..4096 and rows * cols <= 2^24");
+    if (int e = check_image_size("sft_tracker_create", rows, cols)) return e;
     if (n_slots < 1 || n_slots > 65535) return fail(SF_ERR_ARG, "sft_tracker_create: n_slots lies in 1..65535");
     if (max_tracks < 1 || max_tracks > SFT_MAX_TRACKS) return fail(SF_ERR_ARG, "sft_tracker_create: max_tracks lies in 1..256");
     HIP_TRY(hipSetDevice(h->device));
@@ -326,7 +299,7 @@ void sft_tracker_destroy(sft_tracker *t) {
         (void)hipStreamSynchronize(h->stream);
         h->trackers.erase(std::remove(h->trackers.begin(), h->trackers.end(), t), h->trackers.end());
         h->own.free_device(t->state);
-        h->own.free_device(t->scratch);
+        h->own.free_device(t->scratch.dev);
     }  // else: sf_destroy of the handle already released the memory and left the tracker as an empty shell
     delete t;
 }
@@ -352,18 +325,18 @@ int sft_slot_info(sft_tracker *t, int slot, sft_slot *slot_out) {
 
 int sft_reset_slots(sft_tracker *t, int n, const int32_t *slots, int restart_ids) {
     if (int e = check_tracker("sft_reset_slots", t)) return e;
-    if (n < 0) return fail(SF_ERR_ARG, "sft_reset_slots: n < 0");
+    if (int e = check_batch("sft_reset_slots", n)) return e;
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, "sft_reset_slots: more than 65535 entries in one call");
     if (!slots) return fail(SF_ERR_ARG, "sft_reset_slots: null argument");
     for (int q = 0; q < n; q++)
         if (slots[q] < 0 || slots[q] >= t->n_slots) return fail(SF_ERR_ARG, "sft_reset_slots: slot out of range");
     sf_handle *h = t->h;
     HIP_TRY(hipSetDevice(h->device));
-    if (int e = dev_grow(h, &t->scratch, &t->scratch_bytes, (size_t)n * 4)) return e;
-    t->slots_host.assign(slots, slots + n);
-    HIP_TRY(hipMemcpyAsync(t->scratch, t->slots_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(sft_reset_kernel, dim3((unsigned)((n + SFT_NT - 1) / SFT_NT)), dim3(SFT_NT), 0, h->stream, t->state, t->lay, (const int *)t->scratch, n,
+    if (int e = t->scratch.grow(h->own, (size_t)n * 4, h->stream)) return e;
+    int32_t *stab = t->scratch.resized<int32_t>((size_t)n, 1);
+    std::memcpy(stab, slots, (size_t)n * 4);
+    if (int e = t->scratch.upload(0, stab, (size_t)n * 4, h->stream)) return e;
+    hipLaunchKernelGGL(sft_reset_kernel, dim3((unsigned)((n + SFT_NT - 1) / SFT_NT)), dim3(SFT_NT), 0, h->stream, t->state, t->lay, (const int *)t->scratch.dev, n,
                        restart_ids != 0);
     HIP_TRY(hipGetLastError());
     for (int q = 0; q < n; q++) t->has_prev[(size_t)slots[q]] = 0;

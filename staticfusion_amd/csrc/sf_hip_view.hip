@@ -1,9 +1,9 @@
 // sf_hip_view.hip — libsf_hip.so, the interface of include/sf_view.h (symbols sfv_*): surfel buffers drawn from any pose with
 // any pinhole intrinsics into depth, colour and index images (kernels: sf_view.h). A render only reads its maps. Everything
-// it writes lies in one block of the handle (sf_handle::view_scratch), grown when a call needs more and freed with the
-// handle: argument tables, one ray table per distinct (rows, cols, cx, cy, fx, fy) of the call, per view a key image, a
-// large-sprite list and -- for the host-pointer calls -- the images before they are copied out. It uses no scratch of a map,
-// no key image or density flag of the prediction, no image of a stream and not the handle's shared argument table.
+// it writes lies in the call block sf_handle::view (sf_call_block.h: layout, growth and lifetime): argument tables, one ray
+// table per distinct (rows, cols, cx, cy, fx, fy) of the call, per view a key image, a large-sprite list and -- for the
+// host-pointer calls -- the images before they are copied out. It uses no scratch of a map, no key image or density flag of
+// the prediction, no image of a stream and not the handle's shared argument table.
 #include "../../include/sf_view.h"
 #include "sf_host.h"
 #include "sf_view.h"
@@ -13,11 +13,8 @@ static_assert(sizeof(sfv_view) == 112, "include/sf_view.h: sfv_view is 112 bytes
 
 static int check_view(const sfv_view *v) {
     if (!v) return fail(SF_ERR_ARG, "sfv: null view");
-    bool finite = true;
-    for (int k = 0; k < 16; k++) finite = finite && std::isfinite(v->pose[k]);
-    finite = finite && std::isfinite(v->cx) && std::isfinite(v->cy) && std::isfinite(v->fx) && std::isfinite(v->fy) &&
-             std::isfinite(v->min_confidence) && std::isfinite(v->max_depth);
-    if (!finite) return fail(SF_ERR_ARG, "sfv: NaN or inf in a view");
+    if (!finite_all(v->pose, 16) || !finite_all(&v->cx, 4) || !std::isfinite(v->min_confidence) || !std::isfinite(v->max_depth))
+        return fail(SF_ERR_ARG, "sfv: NaN or inf in a view");
     if (v->rows < 1 || v->rows > 4096 || v->cols < 1 || v->cols > 4096) return fail(SF_ERR_ARG, "sfv: rows and cols of a view lie in 1..4096");
     if (v->fx == 0.f || v->fy == 0.f) return fail(SF_ERR_ARG, "sfv: fx or fy of a view is 0");
     if (!(v->max_depth > 0.4f)) return fail(SF_ERR_ARG, "sfv: max_depth of a view must exceed 0.4");
@@ -56,12 +53,13 @@ void sfv_plan(ViewPlan &p, int n, const ViewJob *jobs, const sfv_view *views, in
     }
 }
 
-int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const sfv_view *views, const ViewOut *outs, unsigned char *base,
-                  std::vector<unsigned char> &tab_host, const float *upload, int upload_count) {
+int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const sfv_view *views, const ViewOut *outs, SfCallBlock &blk,
+                  const float *upload, int upload_count) {
     const int n = p.n;
-    tab_host.resize(p.o_counters);
-    ViewArgs *tab = (ViewArgs *)(tab_host.data() + p.o_tab);
-    ViewRayArgs *rtab = (ViewRayArgs *)(tab_host.data() + p.o_rtab);
+    unsigned char *base = blk.dev;
+    unsigned char *tab_host = blk.resized<unsigned char>(p.o_counters);  // both tables, as they lie in the block
+    ViewArgs *tab = (ViewArgs *)(tab_host + p.o_tab);
+    ViewRayArgs *rtab = (ViewRayArgs *)(tab_host + p.o_rtab);
     int max_count = 0;
     size_t max_px = 0, max_ray_px = 0;
     for (size_t r = 0; r < p.ray_first.size(); r++) {
@@ -93,7 +91,7 @@ int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const sf
         max_count = std::max(max_count, a.count);
         max_px = std::max(max_px, (size_t)v.rows * v.cols);
     }
-    HIP_TRY(hipMemcpyAsync(base, tab_host.data(), p.o_counters, hipMemcpyHostToDevice, h->stream));
+    if (int e = blk.upload(0, tab_host, p.o_counters, h->stream)) return e;
     if (upload_count) HIP_TRY(hipMemcpyAsync(base + p.o_upload, upload, (size_t)upload_count * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     const ViewArgs *d_tab = (const ViewArgs *)(base + p.o_tab);
     const unsigned nv = (unsigned)n;
@@ -127,8 +125,8 @@ static int render(sf_handle *h, int n, const ViewJob *jobs, const sfv_view *view
         }
         max_tiles = std::max(max_tiles, ((views[q].rows + SFV_T - 1) / SFV_T) * ((views[q].cols + SFV_T - 1) / SFV_T));
     }
-    if (int e = dev_grow(h, &h->view_scratch, &h->view_bytes, p.off)) return e;
-    unsigned char *base = h->view_scratch;
+    if (int e = h->view.grow(h->own, p.off, h->stream)) return e;
+    unsigned char *base = h->view.dev;
     std::vector<ViewOut> staged;
     if (!device_out) {
         staged.resize((size_t)n);
@@ -136,7 +134,7 @@ static int render(sf_handle *h, int n, const ViewJob *jobs, const sfv_view *view
             staged[(size_t)q] = ViewOut{outs[q].depth ? base + o_depth[(size_t)q] : nullptr, outs[q].rgb ? base + o_rgb[(size_t)q] : nullptr,
                                         outs[q].index ? base + o_index[(size_t)q] : nullptr};
     }
-    if (int e = sfv_draw_keys(h, p, jobs, views, device_out ? outs : staged.data(), base, h->view_tab_host, upload, upload_count)) return e;
+    if (int e = sfv_draw_keys(h, p, jobs, views, device_out ? outs : staged.data(), h->view, upload, upload_count)) return e;
     hipLaunchKernelGGL(sfv_resolve_kernel, dim3((unsigned)max_tiles, (unsigned)n), dim3(256), 0, h->stream, (const ViewArgs *)(base + p.o_tab));
     HIP_TRY(hipGetLastError());
     h->view_counters_off = p.o_counters;
@@ -156,7 +154,7 @@ static int render_maps(const char *what, sf_handle *h, int n, sf_map *const *map
                        void *const *index_out, bool device_out) {
     if (!h || n < 0 || (n && (!maps || !views))) return fail(SF_ERR_ARG, std::string(what) + ": bad argument");
     if (n == 0) return SF_OK;
-    if (n > 65535) return fail(SF_ERR_ARG, std::string(what) + ": more than 65535 views in one call");
+    if (int e = check_batch(what, n, "views")) return e;
     std::vector<ViewJob> jobs((size_t)n);
     std::vector<ViewOut> outs((size_t)n);
     for (int q = 0; q < n; q++) {
@@ -211,9 +209,9 @@ int sfv_render_surfels(sf_handle *h, const float *surfels, int count, int tick, 
 
 int sfv_last_large_sprites(sf_handle *h, int n, int32_t *counts) {
     if (!h || !counts || n < 0) return fail(SF_ERR_ARG, "sfv_last_large_sprites: bad argument");
-    if (n != h->view_last_n || !h->view_scratch) return fail(SF_ERR_STATE, "sfv_last_large_sprites: n is not the n of the handle's last render call");
+    if (n != h->view_last_n || !h->view.dev) return fail(SF_ERR_STATE, "sfv_last_large_sprites: n is not the n of the handle's last render call");
     if (n == 0) return SF_OK;
-    return d2h(h, counts, h->view_scratch + h->view_counters_off, (size_t)n * sizeof(int32_t));
+    return d2h(h, counts, h->view.dev + h->view_counters_off, (size_t)n * sizeof(int32_t));
 }
 
 }  // extern "C"

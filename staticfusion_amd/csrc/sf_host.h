@@ -1,7 +1,10 @@
 // sf_host.h — what the host-side translation units of libsf_hip.so share: the handle, the error helpers, device
-// allocation, and the few functions one part calls in another. Nothing here is exported (include/sf.h is the ABI).
+// allocation, the refusals that every companion interface states the same way, and the few functions one part calls in
+// another. Nothing here is exported (include/sf.h is the ABI).
 //   sf_resources.h     the owner of every device block, pinned block, event and stream (SfOwner), the one growth rule
 //                      (SfOwner::grow, here dev_grow) and the ring of per-call tables (SfRing); host only, no kernel
+//   sf_call_block.h    the per-call block of a companion interface: its layout rule (SfPlan), the block with the host copies
+//                      of its tables (SfCallBlock) and the rules of their lifetime; host only, no kernel
 //   sf_hip.hip         handle lifetime, parameters, the builds of the frame kernel, launch()
 //   sf_hip_solver.hip  images in, frames (one or several per launch), results and debug planes out, measurement support
 //   sf_hip_input.hip   the input stage: loader decimation / RGB -> intensity, bilateral depth filter (sf_input.h)
@@ -9,8 +12,9 @@
 //                      check and the table upload of every part that takes maps (check_map, upload_table)
 //   sf_hip_migrate.hip single streams between handles, to and from host memory, back to constructor state (sf_migrate.h;
 //                      its interface is include/sf_migrate.h, symbols sfm_*)
-//   sf_hip_map_window.hip  bounded maps: count, cull, extract, page out, append (sf_map_window.h; its interface is
-//                      include/sf_map_window.h, symbols sfw_*)
+//   sf_hip_map_window.hip  bounded maps: count, cull, extract, page out, append (sf_map_window.h, sf_window_args.h; its
+//                      interface is include/sf_map_window.h, symbols sfw_*); the one compiled copy of the scan and the
+//                      ordered write, which the join and the body maps launch through sfw_launch_scan / sfw_launch_write
 //   sf_hip_view.hip    maps drawn from any view: depth, colour and index images (sf_view.h; its interface is
 //                      include/sf_view.h, symbols sfv_*)
 //   sf_hip_score.hip   poses scored against maps: frame-to-map agreement counts (sf_score.h; its interface is
@@ -42,7 +46,7 @@
 
 #include "sf_cluster.h"
 #include "sf_device_common.h"
-#include "sf_resources.h"  // SF_INTERNAL, sf_fail, SfOwner, SfRing
+#include "sf_call_block.h"  // SfPlan, SfCallBlock; sf_resources.h: SF_INTERNAL, sf_fail, SfOwner, SfRing
 
 // the two builds of the frame kernels (sf_frame_kernels.hip, -DSF_NT=256 / -DSF_NT=1024)
 struct FrameVariant {
@@ -121,56 +125,21 @@ struct sf_handle {
     hipEvent_t mig_ev = nullptr;
     uint8_t *mig_stage = nullptr;
     size_t mig_stage_bytes = 0;
-    // free-view rendering (sf_hip_view.hip): one block for the key images, ray tables, large-sprite lists, argument tables and
-    // output staging of a call, grown when a call needs more (dev_grow); the host copy
-    // the tables are filled from; where the per-view list counters of the last call lie in the block
-    unsigned char *view_scratch = nullptr;
-    size_t view_bytes = 0;
-    std::vector<unsigned char> view_tab_host;
-    size_t view_counters_off = 0;
+    // The companion interfaces: per part one call block (sf_call_block.h: device memory grown when a call needs more, the host
+    // copies its tables are filled from, and the rules of their lifetime). What lies in each is its file's business.
+    SfCallBlock view;       // sf_hip_view.hip: free-view rendering
+    size_t view_counters_off = 0;  // where the per-view list counters of the last render call lie in `view`, and its n
     int view_last_n = 0;
-    // pose scoring (sf_hip_score.hip): a block of its own with the same drawing layout (ViewPlan) followed by the score
-    // table, the result records and -- for the host-pointer calls -- the uploaded frames and the class images
-    unsigned char *score_scratch = nullptr;
-    size_t score_bytes = 0;
-    std::vector<unsigned char> score_tab_host, score_args_host;  // the host copies of the view table and the score table
-    // place recognition (sf_hip_keyframes.hip): live keyframe databases created from this handle: sf_destroy releases their
-    // memory and orphans them, like the maps
+    SfCallBlock score;      // sf_hip_score.hip: the drawing layout (ViewPlan), then the score table, records, frames
+    SfCallBlock regions;    // sf_hip_regions.hip
+    SfCallBlock align;      // sf_hip_align.hip: the drawing layout, then the entry table with the states, images, systems
+    SfCallBlock join;       // sf_hip_join.hip
+    SfCallBlock bodies;     // sf_hip_bodies.hip: host copy 0 the entry table, host copy 1 the pair table
+    SfCallBlock body_maps;  // sf_hip_body_maps.hip
+    // live keyframe databases and trackers created from this handle (sf_hip_keyframes.hip, sf_hip_tracks.hip): sf_destroy
+    // releases their memory and orphans them, like the maps. A tracker's blocks are blocks of `own`, a database has an owner.
     std::vector<struct sfk_db *> keyframe_dbs;
-    // moving regions (sf_hip_regions.hip): one block for the entry table, the provisional label and count images, the block
-    // counts and -- for the host forms -- the uploaded frames, records and label images of a call, grown when a call needs
-    // more (dev_grow); the host copy the entry table is filled from
-    unsigned char *regions_scratch = nullptr;
-    size_t regions_bytes = 0;
-    std::vector<unsigned char> regions_args_host;
-    // pose refinement (sf_hip_align.hip): a block of its own with the drawing layout (ViewPlan) followed by the entry table
-    // with the entries' states, the model images, the systems, the result records and -- for the host-pointer calls -- the
-    // uploaded frames; the host copies of the view table and the entry table
-    unsigned char *align_scratch = nullptr;
-    size_t align_bytes = 0;
-    std::vector<unsigned char> align_tab_host, align_args_host;
-    // joined and thinned maps (sf_hip_join.hip): one block for the two entry tables, the counters, the voxel tables, the
-    // remembered slots, the ballots and the block counts of a call, grown when a call needs more (dev_grow); the host copy
-    // the tables are filled from
-    unsigned char *join_scratch = nullptr;
-    size_t join_bytes = 0;
-    std::vector<unsigned char> join_args_host;
-    // region tracks (sf_hip_tracks.hip): live trackers created from this handle. Their state and scratch are blocks of `own`;
-    // sf_destroy releases them with it and orphans the trackers, like the keyframe databases
     std::vector<struct sft_tracker *> trackers;
-    // region motion (sf_hip_bodies.hip): one block for the entry table, the pair table, the region states, the systems, the
-    // model images and -- for the host form -- the uploaded frames and the results of a call, grown when a call needs more
-    // (dev_grow); the host copies the two tables are filled from
-    unsigned char *bodies_scratch = nullptr;
-    size_t bodies_bytes = 0;
-    std::vector<unsigned char> bodies_args_host;
-    std::vector<int32_t> bodies_pairs_host;
-    // body maps (sf_hip_body_maps.hip): one block for the two entry tables, the counters, the voxel tables with their bids, the
-    // candidates' slots, the merge table, the ballots, the block counts and -- for the host form -- the uploaded frames of a
-    // call, grown when a call needs more (dev_grow); the host copy the tables are filled from
-    unsigned char *body_maps_scratch = nullptr;
-    size_t body_maps_bytes = 0;
-    std::vector<unsigned char> body_maps_args_host;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -230,6 +199,43 @@ static int dev_grow(sf_handle *h, T **p, size_t *capacity, size_t count) {
     return h->own.grow(p, capacity, count, h->stream);
 }
 
+// ---- the shared refusal list of the companion interfaces. Each takes the caller's name (or its prefix), so a refusal names
+// its function; a caller makes them in the order its header promises, and a refused call has changed nothing.
+enum CallForm { FORM_STREAMS, FORM_HOST, FORM_DEVICE };  // the inputs of a call: the handle's streams, host images, device images
+// the batch bound: n entries, at most 65535 (grid.y); n == 0 is the caller's to answer
+static inline int check_batch(const std::string &w, int n, const char *noun = "entries") {
+    if (n < 0) return fail(SF_ERR_ARG, w + ": n < 0");
+    if (n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 " + noun + " in one call");
+    return SF_OK;
+}
+// the image-size rule of the calls that take frames of a size of their own
+static inline int check_image_size(const std::string &w, int rows, int cols) {
+    if (rows < 1 || rows > 4096 || cols < 1 || cols > 4096 || (long long)rows * cols > (1ll << 24))
+        return fail(SF_ERR_ARG, w + ": rows and cols lie in 1..4096 and rows * cols <= 2^24");
+    return SF_OK;
+}
+static inline bool finite_all(const float *p, int n) {
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+// sft_camera, sfb_camera, sfp_camera (one layout: their files assert it): pose[16], then cx, cy, fx, fy
+template <class Camera>
+static int check_camera(const char *prefix, const Camera *c) {
+    if (!finite_all(c->pose, 16) || !finite_all(&c->cx, 4)) return fail(SF_ERR_ARG, std::string(prefix) + ": NaN or inf in a camera");
+    if (c->fx == 0.f || c->fy == 0.f) return fail(SF_ERR_ARG, std::string(prefix) + ": fx or fy is 0");
+    return SF_OK;
+}
+// the distinct-maps check, entry by entry: maps[q] is none of maps[0 .. q)
+static inline int check_distinct(const std::string &w, sf_map *const *maps, int q, const char *twice) {
+    for (int r = 0; r < q; r++)
+        if (maps[r] == maps[q]) return fail(SF_ERR_ARG, w + ": " + twice);
+    return SF_OK;
+}
+// the rule AFTER A CALL THAT CHANGES A MAP of include/sf_map_window.h: surfel indices have moved, so the index image of the
+// last fuse no longer describes the map
+static inline void indices_moved(sf_map *m) { m->have_index = false; }
+
 // shared between the parts (defined in the file named)
 SF_INTERNAL int launch(sf_handle *h, int mask, int im_count, int n_frames = 1, const FrameLaunch *ml = nullptr);  // sf_hip.hip
 SF_INTERNAL int solve_mask(const sf_handle *h, int create_image_pyr);                                            // sf_hip.hip
@@ -247,22 +253,23 @@ struct ViewJob {
 struct ViewOut {
     void *depth, *rgb, *index;  // device pointers of the resolve kernel's outputs, any of them null
 };
-struct ViewPlan {
+struct ViewPlan : SfPlan {
     int n = 0;
     std::vector<int> ray_of;     // per view: its ray table
     std::vector<int> ray_first;  // per ray table: the view that introduced it
-    size_t off = 0;              // bytes laid out so far
     size_t o_tab = 0, o_rtab = 0, o_counters = 0, o_upload = 0;
     std::vector<size_t> o_rays, o_keys, o_list;
-    size_t take(size_t bytes) {  // 256-byte aligned
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
 };
 SF_INTERNAL void sfv_plan(ViewPlan &p, int n, const ViewJob *jobs, const struct sfv_view *views, int upload_count);
+// (blk: the caller's block, grown to p.off bytes; the view tables are filled into its host copy 0)
 SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jobs, const struct sfv_view *views, const ViewOut *outs,
-                              unsigned char *base, std::vector<unsigned char> &tab_host, const float *upload, int upload_count);
+                              SfCallBlock &blk, const float *upload, int upload_count);
+// The scan and the ordered write of sf_map_window.h for whoever has filled ballots and block counts of its own (the join, the
+// body maps), on the handle's stream (sf_hip_map_window.hip: the library holds these kernels once): sfw_scan_kernel over n
+// entries of a device table, sfw_write_kernel<false> over (blocks, n).
+struct WindowArgs;  // sf_window_args.h
+SF_INTERNAL void sfw_launch_scan(sf_handle *h, const WindowArgs *d_tab, int n);
+SF_INTERNAL void sfw_launch_write(sf_handle *h, const WindowArgs *d_tab, unsigned blocks, int n);
 SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
 SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
 // sf_hip_bodies.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the region

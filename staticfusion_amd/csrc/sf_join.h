@@ -20,12 +20,9 @@
 #include "sf_join_key.h"
 #include "sf_records.h"
 
-// The scan and the ordered write are those of sf_map_window.h, the same text. It is included into a namespace because its scan
-// kernel is not a template: host_map_window.o defines it for the library, and a second definition of that name would not link.
-namespace sfj_window {
-#include "sf_map_window.h"
-}
-using sfj_window::WindowArgs;
+// The scan and the ordered write are those of sf_map_window.h, launched by sfw_launch_scan / sfw_launch_write (sf_host.h): the
+// host fills a WindowArgs beside every JoinArgs.
+#include "sf_window_args.h"
 
 #define SFJ_BLOCK SFW_BLOCK
 #define SFJ_WAVES SFW_WAVES

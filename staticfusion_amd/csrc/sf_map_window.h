@@ -6,26 +6,11 @@
 #pragma once
 #include "sf_device_common.h"
 #include "sf_records.h"  // load_policy
+#include "sf_window_args.h"  // WindowArgs, SFW_BLOCK, SFW_WAVES
 
-#define SFW_BLOCK 256  // surfels per workgroup (SF_CLEAN_BLOCK's reasoning: a QVGA map still covers the CUs)
-#define SFW_WAVES (SFW_BLOCK / 64)
 // load policy of the record reads when SF_WINDOW_POLICY is not set: 0 default, 1 the move pass non-temporal, 2 both passes
 #define SFW_DEFAULT_POLICY 0
 
-struct WindowArgs {
-    const float *src;  // count x 12 (the map's buf[0])
-    float *dst;        // the map's idle buffer
-    int count;
-    int move_rest;     // 0: only the selected surfels are moved (cull, extract: nobody reads [k, count) of dst)
-    // the filter (include/sf_map_window.h); a disabled test has use_* == 0
-    int use_conf, use_age, use_radius, invert;
-    float min_confidence;
-    float tick, max_age;     // (float)tick of the map, (float)max_age
-    float cx, cy, cz, r2;    // centre, radius * radius
-    unsigned long long *ballots;  // [ceil(count / 64)]: bit l of word w = surfel 64 w + l is selected
-    int *block_counts;            // [ceil(count / SFW_BLOCK)]: selected per block; the scan turns them into exclusive offsets
-    int *result;                  // [0]: k, the number selected
-};
 // Every kernel works on table entry blockIdx.y (the scan: blockIdx.x); grid.x is sized for the largest map of the batch and
 // workgroups beyond a map's own extent leave at once.
 

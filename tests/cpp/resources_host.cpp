@@ -1,5 +1,5 @@
-// The host-side resource owner (staticfusion_amd/csrc/sf_resources.h: SfOwner, its growth rule, SfRing) played through on the
-// CPU. Stand-alone: the HIP functions the header calls are defined HERE -- malloc-backed, with a set of live pointers (a free
+// The host-side resource owner (staticfusion_amd/csrc/sf_resources.h: SfOwner, its growth rule, SfRing) and the per-call block
+// of the companion interfaces (sf_call_block.h: SfPlan, SfCallBlock) played through on the CPU. Stand-alone: the HIP functions the header calls are defined HERE -- malloc-backed, with a set of live pointers (a free
 // of an unknown one aborts), a log of calls and "fail the k-th acquiring call" --, and so is sf_fail. No HIP runtime, no
 // library. tests/test_host_resources_cpu.py compiles it with -fsanitize=address,undefined and runs it as a child process: once
 // without a failure, then once for every acquiring call of that run failing. It prints "ok <runs>" and returns 0, or names
@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <map>
 
-#include "../../staticfusion_amd/csrc/sf_resources.h"
+#include "../../staticfusion_amd/csrc/sf_call_block.h"  // (includes sf_resources.h)
 
 // ---- the HIP runtime of this program ---------------------------------------------------------------------------------
 enum Op { MALLOC, FREE, HOST_MALLOC, HOST_FREE, EVENT_CREATE, EVENT_DESTROY, STREAM_CREATE, STREAM_DESTROY, STREAM_SYNC, EVENT_SYNC, EVENT_RECORD, MEMCPY, MEMSET };
@@ -18,6 +18,12 @@ struct Call {
 };
 static std::map<const void *, Op> live;  // pointer -> the call that made it
 static std::vector<Call> calls;
+struct Fill {  // a queued hipMemsetAsync
+    const unsigned char *p;
+    int value;
+    size_t bytes;
+};
+static std::vector<Fill> fills;
 static int acquired = 0;   // acquiring calls so far in this run
 static int fail_at = 0;    // the acquiring call that fails (1-based), 0: none
 static bool fired = false; // ... and it has
@@ -98,6 +104,13 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKin
     calls.push_back({MEMCPY, dst});
     return hipSuccess;
 }
+hipError_t hipMemsetAsync(void *p, int v, size_t bytes, hipStream_t s) {  // (p may lie inside a block: the caller checks the range)
+    must_be_live(s, STREAM_CREATE);
+    std::memset(p, v, bytes);
+    fills.push_back({(const unsigned char *)p, v, bytes});
+    calls.push_back({MEMSET, p});
+    return hipSuccess;
+}
 const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "unknown error"; }
 }
 
@@ -164,6 +177,31 @@ static int call_local(bool leave_early) {  // like sf_microbench_copy: everythin
     if (leave_early) return SF_OK;
     if (int e = call.event(&e1, hipEventDefault)) return e;
     return SF_OK;
+}
+
+// ---- a companion call in miniature (sf_hip_join.hip's shape): lay out, grow, take the zeroed table, fill, upload, clear
+struct Rec {
+    int a, b;
+    void *p;
+};
+static int zero_pieces, ones_pieces, rest_pieces;  // the layout of the next block_call, in pieces of `piece` bytes
+static int block_call(Mini &m, SfCallBlock &blk, size_t n, size_t piece, SfPlan *plan_out) {
+    SfPlan p;
+    const size_t o_tab = p.take(n * sizeof(Rec));
+    p.zeros_from_here();
+    for (int q = 0; q < zero_pieces; q++) p.take(piece);
+    p.ones_from_here();
+    for (int q = 0; q < ones_pieces; q++) p.take(piece);
+    p.rest_from_here();
+    for (int q = 0; q < rest_pieces; q++) p.take(piece);
+    *plan_out = p;
+    if (int e = blk.grow(m.own, p.off, m.stream)) return e;
+    Rec *tab = blk.zeroed<Rec>(n);
+    for (size_t q = 0; q < n; q++)
+        if (tab[q].a || tab[q].b || tab[q].p) return sf_fail(SF_ERR_STATE, "a table handed out zeroed is not zero");
+    for (size_t q = 0; q < n; q++) tab[q] = Rec{(int)q + 1, -1, &blk};  // (every byte a later, smaller call must not see)
+    if (int e = blk.upload(o_tab, tab, n * sizeof(Rec), m.stream)) return e;
+    return p.clear(blk.dev, m.stream);
 }
 
 // One step. If the run's failing call fell into it: the documented code came back, `untouched` holds (what the step would
@@ -298,6 +336,64 @@ static int scenario(int failing, int *acquiring_calls) {
             CHECK(count_op(mark, EVENT_SYNC) == (i >= 8 ? 1u : 0u) && copied >= 0 && (i < 8 || (waited >= 0 && waited < copied)));
             CHECK(m.eager.done(m.stream) == SF_OK);
             CHECK(calls.back().op == EVENT_RECORD && calls.back().p == m.eager.event[slot]);
+        }
+
+        // ---- the layout rule: 256-byte aligned, monotonic, the next piece never inside the last one
+        {
+            SfPlan p;
+            size_t last = 0, last_bytes = 0;
+            const size_t sizes[] = {0, 1, 255, 256, 257, 48, 4096, 3, 0, 0, 1000001};
+            for (size_t q = 0; q < sizeof sizes / sizeof sizes[0]; q++) {
+                const size_t o = p.take(sizes[q]);
+                CHECK(o % 256 == 0 && p.off % 256 == 0 && o >= last + last_bytes && p.off >= o + sizes[q] && p.off < o + sizes[q] + 256);
+                last = o;
+                last_bytes = sizes[q];
+            }
+        }
+        // ---- a call block: a small call, a larger one that outgrows the block, the small one again; the cleared ranges with
+        // an empty zero range, an empty ones range, an empty rest and none empty
+        {
+            SfCallBlock blk;
+            SfPlan p;
+            const int layouts[5][3] = {{2, 3, 1}, {0, 2, 1}, {2, 0, 1}, {2, 3, 0}, {0, 0, 0}};
+            const size_t ns[3] = {3, 40, 3}, pieces[3] = {100, 5000, 100};
+            for (int l = 0; l < 5; l++)
+                for (int c = 0; c < 3; c++) {
+                    zero_pieces = layouts[l][0]; ones_pieces = layouts[l][1]; rest_pieces = layouts[l][2];
+                    unsigned char *const dev0 = blk.dev;
+                    const size_t bytes0 = blk.bytes;
+                    const std::vector<unsigned char> host0 = blk.host[0];
+                    mark = calls.size();
+                    const size_t fills0 = fills.size();
+                    // (a failing acquisition: the pointer, the capacity and the host copy are what they were before the call)
+                    if (step([&] { return block_call(m, blk, ns[c], pieces[c], &p); }, [&] { return blk.dev == dev0 && blk.bytes == bytes0 && blk.host[0] == host0; })) return 1;
+                    CHECK(blk.bytes >= p.off && blk.host[0].size() == ns[c] * sizeof(Rec));
+                    CHECK(std::memcmp(blk.dev, blk.host[0].data(), blk.host[0].size()) == 0);  // the table is at its offset, 0
+                    if (blk.dev != dev0 && dev0) {  // outgrown: the new block, the drain, and only then the old one freed, once
+                        const long made = find_op(mark, MALLOC, blk.dev), drained = find_op(mark, STREAM_SYNC, m.stream), freed = find_op(mark, FREE, dev0);
+                        CHECK(made >= 0 && made < drained && drained < freed && count_op(mark, FREE) == 1);
+                    } else {
+                        CHECK(count_op(mark, FREE) == 0 && (dev0 == nullptr || count_op(mark, MALLOC) == 0));
+                    }
+                    // the two fills cover exactly what lies between the marks, the ones directly behind the zeros
+                    CHECK(fills.size() == fills0 + 2);
+                    const Fill &z = fills[fills0], &o = fills[fills0 + 1];
+                    const size_t piece_room = (pieces[c] + 255) / 256 * 256;
+                    CHECK(z.value == 0 && z.p == blk.dev + p.o_zero && z.bytes == zero_pieces * piece_room);
+                    CHECK(o.value == 0xFF && o.p == z.p + z.bytes && o.bytes == ones_pieces * piece_room);
+                    CHECK(p.o_zero == (ns[c] * sizeof(Rec) + 255) / 256 * 256 && p.o_rest == p.o_zero + z.bytes + o.bytes);
+                    CHECK(p.off == p.o_rest + rest_pieces * piece_room && p.off <= blk.bytes);
+                    for (size_t q = 0; q < z.bytes; q++) CHECK(z.p[q] == 0);
+                    for (size_t q = 0; q < o.bytes; q++) CHECK(o.p[q] == 0xFF);
+                }
+            CHECK(blk.bytes >= 40 * sizeof(Rec) + 5 * 5120);  // it did grow past its first size
+            // a second host copy is independent of the first; a resized table keeps what it held
+            int *second = blk.resized<int>(4, 1);
+            second[3] = 7;
+            CHECK(blk.host[0].size() == 3 * sizeof(Rec) && blk.resized<int>(6, 1)[3] == 7 && blk.resized<int>(6, 1)[5] == 0);
+            m.own.free_device(blk.dev);
+            blk.forget();
+            CHECK(!blk.dev && !blk.bytes);
         }
 
         // ---- an owner on the stack, left by an early return and by the last one

@@ -10,7 +10,10 @@ Required: the same object names in both trees and no difference at all.
 
 Should a change of include order permute whole functions, the objects are compared once more function by function with
 the `.LBB<n>_` label numbers normalised, and the report says `identical per function`. Anything else is `DIFFERENT` and
-the exit status is 1. Needs hipcc, no GPU.
+the exit status is 1. Where the device side of an object is DIFFERENT because one tree has functions the other lacks (a kernel
+that moved to another object), one more line says whether every function both trees have is identical -- code, kernel
+descriptor and metadata entry, with the `.Lfunc_end<n>` numbers normalised too -- and names the others. The exit status
+stays 1: whether the move was intended is the reader's to judge. Needs hipcc, no GPU.
 """
 import argparse
 import concurrent.futures
@@ -74,6 +77,35 @@ def by_function(asm):
     return parts
 
 
+def common_functions(old, new):
+    """for two device-side listings: (functions only old, only new, functions both have that differ)"""
+    def parts(asm):
+        out, kd, meta, in_meta = {}, None, None, False
+        for name, lines in by_function(asm).items():
+            if name and not name.startswith(("amdhsa.", "__hip_cuid")):
+                out[name] = [re.sub(r"\.Lfunc_(begin|end)\d+|\bBB\d+_", "N_", l) for l in lines]  # (BB<n>_: in the loop comments)
+        for l in asm:
+            if l.strip().startswith(".amdhsa_kernel "):
+                kd = out.setdefault(l.split()[1] + " (descriptor)", [])
+            if kd is not None:
+                kd.append(l)
+            if l.strip() == ".end_amdhsa_kernel":
+                kd = None
+            if l.startswith("amdhsa.kernels:"):
+                in_meta = True
+            elif in_meta and l.startswith("  - "):
+                meta = []
+            elif in_meta and not l.startswith(" "):
+                in_meta = False
+            if in_meta and meta is not None:
+                meta.append(l)
+                if l.strip().startswith(".name:"):
+                    out[l.split()[1] + " (metadata)"] = meta
+        return out
+    fo, fn = parts(old), parts(new)
+    return sorted(set(fo) - set(fn)), sorted(set(fn) - set(fo)), sorted(k for k in fn if k in fo and fo[k] != fn[k])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("old_tree")
@@ -116,6 +148,11 @@ def main():
             print("%-28s %-7s %12d  %s" % (obj, side, instruction_lines(new), verdict))
             if verdict == "DIFFERENT":
                 sys.stdout.writelines(l + "\n" for l in list(difflib.unified_diff(old, new, "old", "new", lineterm="", n=1))[:60])
+                if side == "device":
+                    gone, came, differ = common_functions(old, new)
+                    if (gone or came) and not differ:
+                        print("%-28s %-7s every function both trees have is identical (code, descriptor, metadata); only old: %s; only new: %s"
+                              % (obj, side, gone or "none", came or "none"))
     print("RESULT: %s" % ("DIFFERENT" if bad else "all identical"))
     return bad
 
