@@ -245,6 +245,7 @@ void sf_destroy(sf_handle *h) {
     orphan_maps(h);  // maps outliving their handle: their memory is freed now, every later call on them fails cleanly
     orphan_keyframe_dbs(h);  // and its keyframe databases (sf_hip_keyframes.hip)
     orphan_trackers(h);      // and its region trackers (sf_hip_tracks.hip)
+    orphan_graphs(h);        // and its deformation graphs (sf_hip_deform.hip)
     h->own.release_all();
     delete h;
 }

@@ -33,6 +33,8 @@
 //                      sf_body_world.h; its interface is include/sf_bodies.h, symbols sfb_*); the list of live handles
 //   sf_hip_body_maps.hip  body maps: every moving region fused into a surfel map of its own (sf_body_maps.h,
 //                      sf_body_map_rules.h; its interface is include/sf_body_maps.h, symbols sfp_*)
+//   sf_hip_deform.hip  deformation graphs: maps bent by the nodes of a graph, and the solver for their transforms
+//                      (sf_deform.h, sf_deform_rules.h, sf_deform_solve.h; its interface is include/sf_deform.h, symbols sfd_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -140,6 +142,8 @@ struct sf_handle {
     // releases their memory and orphans them, like the maps. A tracker's blocks are blocks of `own`, a database has an owner.
     std::vector<struct sfk_db *> keyframe_dbs;
     std::vector<struct sft_tracker *> trackers;
+    // and its deformation graphs (sf_hip_deform.hip): each owns its call block through an owner of its own, like a database
+    std::vector<struct sfd_graph *> graphs;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -272,6 +276,7 @@ SF_INTERNAL void sfw_launch_scan(sf_handle *h, const WindowArgs *d_tab, int n);
 SF_INTERNAL void sfw_launch_write(sf_handle *h, const WindowArgs *d_tab, unsigned blocks, int n);
 SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
 SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
+SF_INTERNAL void orphan_graphs(sf_handle *h);        // sf_hip_deform.hip: sf_destroy releases the handle's deformation graphs
 // sf_hip_bodies.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the region
 // motion calls and the body map calls refuse a destroyed handle
 SF_INTERNAL void handle_born(const sf_handle *h);
