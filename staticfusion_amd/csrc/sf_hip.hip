@@ -246,6 +246,7 @@ void sf_destroy(sf_handle *h) {
     orphan_keyframe_dbs(h);  // and its keyframe databases (sf_hip_keyframes.hip)
     orphan_trackers(h);      // and its region trackers (sf_hip_tracks.hip)
     orphan_graphs(h);        // and its deformation graphs (sf_hip_deform.hip)
+    orphan_builders(h);      // and its closure builders (sf_hip_closure.hip)
     h->own.release_all();
     delete h;
 }

@@ -35,6 +35,8 @@
 //                      sf_body_map_rules.h; its interface is include/sf_body_maps.h, symbols sfp_*)
 //   sf_hip_deform.hip  deformation graphs: maps bent by the nodes of a graph, and the solver for their transforms
 //                      (sf_deform.h, sf_deform_rules.h, sf_deform_solve.h; its interface is include/sf_deform.h, symbols sfd_*)
+//   sf_hip_closure.hip loop closures: constraints from two drawings of a place (sf_closure.h, sf_closure_rules.h; its
+//                      interface is include/sf_closure.h, symbols sfc_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,6 +146,8 @@ struct sf_handle {
     std::vector<struct sft_tracker *> trackers;
     // and its deformation graphs (sf_hip_deform.hip): each owns its call block through an owner of its own, like a database
     std::vector<struct sfd_graph *> graphs;
+    // and its closure builders (sf_hip_closure.hip), each with its call block under an owner of its own likewise
+    std::vector<struct sfc_builder *> builders;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
@@ -277,6 +281,7 @@ SF_INTERNAL void sfw_launch_write(sf_handle *h, const WindowArgs *d_tab, unsigne
 SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
 SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
 SF_INTERNAL void orphan_graphs(sf_handle *h);        // sf_hip_deform.hip: sf_destroy releases the handle's deformation graphs
+SF_INTERNAL void orphan_builders(sf_handle *h);      // sf_hip_closure.hip: sf_destroy releases the handle's closure builders
 // sf_hip_bodies.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the region
 // motion calls and the body map calls refuse a destroyed handle
 SF_INTERNAL void handle_born(const sf_handle *h);
