@@ -51,6 +51,29 @@ def binder(prefix, subject, signatures, version, sizes=()):
     return _bind, _product
 
 
+class HandleChild:
+    """base of the wrappers over what a binding creates from a solver's handle (sfk_db, sft_tracker, sfd_graph, sfc_builder):
+    `.solver`, `.api`, the binding `.b`, the pointer under the attribute `_ptr` names, `close()` -- the destroy function
+    `_destroy` names, once, then a null pointer -- and a `__del__` that swallows"""
+
+    _ptr = _destroy = None
+
+    def __init__(self, solver, binding):
+        self.solver, self.api, self.b = solver, solver.api, binding
+        setattr(self, self._ptr, C.c_void_p())
+
+    def close(self):
+        if getattr(self, self._ptr, None):
+            getattr(self.b, self._destroy)(getattr(self, self._ptr))
+            setattr(self, self._ptr, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def one_solver(maps):
     if maps and any(m.solver is not maps[0].solver for m in maps):
         raise SfError("the maps of one call belong to one solver")

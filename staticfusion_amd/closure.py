@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
-from ._companion import binder, map_array, one_solver
+from ._companion import HandleChild, binder, map_array, one_solver
 from .view import SfvView
 
 _H = C.c_void_p
@@ -133,25 +133,14 @@ def link_sample(sa, so, zA, zO, pose_from, pose_to, params=None):
     return int(mask), out[:k.value].copy()
 
 
-class Builder:
+class Builder(HandleChild):
     """one sfc_builder on a solver's handle: `build(maps_new, maps_old, views_from, views_to, params)`, `close()`"""
 
+    _ptr, _destroy = "c", "builder_destroy"
+
     def __init__(self, solver):
-        self.solver, self.api = solver, solver.api
-        self.b = _bind(solver.api)
-        self.c = C.c_void_p()
+        super().__init__(solver, _bind(solver.api))
         self.b.check(self.b.builder_create(solver.h, C.byref(self.c)), "builder_create")
-
-    def close(self):
-        if self.c:
-            self.b.builder_destroy(self.c)
-            self.c = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _arguments(self, maps_new, maps_old, views_from, views_to, params):
         maps_new, maps_old, views_from, views_to = list(maps_new), list(maps_old), list(views_from), list(views_to)

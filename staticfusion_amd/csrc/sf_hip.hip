@@ -89,6 +89,31 @@ int sf_fail(int code, const std::string &msg) {
 static std::mutex g_cluster_mu;
 static hipEvent_t g_cluster_done[64] = {};
 
+// The live handles: sf_create_ex enters a handle, sf_destroy takes it out. A call that is handed a handle and no part of it
+// cannot ask the handle itself whether it still exists (check_live_handle, sf_host.h).
+static std::mutex &live_mutex() {
+    static std::mutex *m = new std::mutex;  // (never destroyed: a call may come during the exit of the process)
+    return *m;
+}
+static std::vector<const sf_handle *> &live_handles() {
+    static std::vector<const sf_handle *> *v = new std::vector<const sf_handle *>;
+    return *v;
+}
+static void handle_born(const sf_handle *h) {
+    std::lock_guard<std::mutex> g(live_mutex());
+    live_handles().push_back(h);
+}
+static void handle_gone(const sf_handle *h) {
+    std::lock_guard<std::mutex> g(live_mutex());
+    auto &v = live_handles();
+    v.erase(std::remove(v.begin(), v.end(), h), v.end());
+}
+bool handle_alive(const sf_handle *h) {
+    std::lock_guard<std::mutex> g(live_mutex());
+    const auto &v = live_handles();
+    return std::find(v.begin(), v.end(), h) != v.end();
+}
+
 // throughput build: the 5-workgroups-per-CU compilation of the frame kernel serves the full solver (Makefile: frame_nt256o5.o)
 bool use_five_per_cu(const sf_handle *h) {
     if (!h->max_blocks_o5) return false;
@@ -236,17 +261,12 @@ static int validate_params(const sf_params *p, int levels) {
     return SF_OK;
 }
 
-// (orphan_maps: sf_hip_model.hip)
 void sf_destroy(sf_handle *h) {
     if (!h) return;
-    handle_gone(h);  // (sf_hip_bodies.hip)
+    handle_gone(h);
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    orphan_maps(h);  // maps outliving their handle: their memory is freed now, every later call on them fails cleanly
-    orphan_keyframe_dbs(h);  // and its keyframe databases (sf_hip_keyframes.hip)
-    orphan_trackers(h);      // and its region trackers (sf_hip_tracks.hip)
-    orphan_graphs(h);        // and its deformation graphs (sf_hip_deform.hip)
-    orphan_builders(h);      // and its closure builders (sf_hip_closure.hip)
+    h->parts.orphan_all();  // what outlives the handle: its memory is freed now, every later call on it fails cleanly (sf_parts.h)
     h->own.release_all();
     delete h;
 }

@@ -3,13 +3,10 @@
 // motion: sf_body_world.h). Everything a call needs lies in the call block sf_handle::bodies (sf_call_block.h: layout, growth
 // and lifetime): the entry table, the pair table, the region states, the model images, the systems and -- for the host form --
 // the uploaded frames and the results. A call only reads its inputs. The number of launches is fixed by the largest
-// `iterations` of the call; nothing is read back between them. This file also keeps the list of live handles, which is how a
-// call on a destroyed handle is refused.
+// `iterations` of the call; nothing is read back between them.
 #include "../../include/sf_bodies.h"
 #include "sf_host.h"
 #include "sf_bodies.h"
-
-#include <mutex>
 
 #define SFB_VERSION 1
 static_assert(sizeof(sfb_params) == 32, "include/sf_bodies.h: sfb_params is 32 bytes");
@@ -22,30 +19,6 @@ static_assert(sizeof(sfb_system) == sizeof(sfa_system) && offsetof(sfb_system, g
 static_assert(SFB_OK == SFA_OK && SFB_FEW_PAIRS == SFA_FEW_PAIRS && SFB_DEGENERATE == SFA_DEGENERATE && SFA_STEP_DEGENERATE == SFB_DEGENERATE,
               "include/sf_bodies.h restates the status codes of include/sf_align.h");
 static_assert(sizeof(BodyState) == 120 && SFB_PB % SFB_NT == 0 && SFB_FIELDS <= 64, "sf_bodies.h: one lane per summed word");
-
-// ---- the live handles: sf_create_ex enters a handle, sf_destroy takes it out
-static std::mutex &live_mutex() {
-    static std::mutex *m = new std::mutex;  // (never destroyed: a call may come during the exit of the process)
-    return *m;
-}
-static std::vector<const sf_handle *> &live_handles() {
-    static std::vector<const sf_handle *> *v = new std::vector<const sf_handle *>;
-    return *v;
-}
-void handle_born(const sf_handle *h) {
-    std::lock_guard<std::mutex> g(live_mutex());
-    live_handles().push_back(h);
-}
-void handle_gone(const sf_handle *h) {
-    std::lock_guard<std::mutex> g(live_mutex());
-    auto &v = live_handles();
-    v.erase(std::remove(v.begin(), v.end(), h), v.end());
-}
-bool handle_alive(const sf_handle *h) {
-    std::lock_guard<std::mutex> g(live_mutex());
-    const auto &v = live_handles();
-    return std::find(v.begin(), v.end(), h) != v.end();
-}
 
 static_assert(offsetof(sfb_params, damping) == 12, "the four floats of sfb_params are consecutive");
 static int check_params(const sfb_params *p) {
@@ -67,7 +40,7 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
                     const int32_t *pairs, const sfb_params *params, int max_regions, void *motions, void *systems_out) {
     const std::string w(what);
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
-    if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
+    if (int e = check_live_handle(w, h)) return e;
     if (n == 0) return SF_OK;
     if (int e = check_batch(w, n)) return e;
     if (!depth0 || !labels0 || !depth1 || !cams0 || !cams1 || !n_regions || !params || !motions) return fail(SF_ERR_ARG, w + ": null argument");

@@ -53,7 +53,7 @@ static int fuse(const char *what, bool device_form, sf_handle *h, int rows, int 
                 sfp_counts *counts_out) {
     const std::string w(what);
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
-    if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
+    if (int e = check_live_handle(w, h)) return e;
     if (n == 0) return SF_OK;
     if (int e = check_batch(w, n)) return e;
     if (!depth || !labels || !cams || !region_labels || !maps || !params || !counts_out) return fail(SF_ERR_ARG, w + ": null argument");
@@ -229,7 +229,7 @@ int sfp_merge_surfel(const sfp_params *p, const float s[12], const float pixel[1
 int sfp_move_maps(sf_handle *h, int n, sf_map *const *maps, const float *W) {
     const std::string w("sfp_move_maps");
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
-    if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
+    if (int e = check_live_handle(w, h)) return e;
     if (n == 0) return SF_OK;
     if (int e = check_batch(w, n)) return e;
     if (!maps) return fail(SF_ERR_ARG, w + ": null argument");

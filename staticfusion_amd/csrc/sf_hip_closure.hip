@@ -22,10 +22,9 @@ static_assert(SFC_FOUND_BOTH == SFC_BIT_BOTH && SFC_FOUND_NEAR == SFC_BIT_NEAR &
                   SFC_FOUND_PIN == SFC_BIT_PIN && SFC_FOUND_LINK_DROPPED == SFC_BIT_LINK_DROPPED && SFC_FOUND_PIN_DROPPED == SFC_BIT_PIN_DROPPED,
               "sf_closure_rules.h restates the bits of include/sf_closure.h");
 
-struct sfc_builder {
-    sf_handle *h = nullptr;  // null: the handle has been destroyed
-    SfCallBlock blk;         // host copy 0: the view tables of the drawing stage; host copy 1: the entry table
-    SfOwner own;
+struct SF_INTERNAL sfc_builder : SfPart {
+    SfCallBlock blk;  // host copy 0: the view tables of the drawing stage; host copy 1: the entry table
+    void shelled() override { blk.forget(); }
 };
 
 static int check_params(const sfc_params *p) {
@@ -42,22 +41,6 @@ static int check_params(const sfc_params *p) {
 }
 
 static SfcRule rule_of(const sfc_params &p) { return SfcRule{p.pins, p.gate_abs, p.gate_rel, p.min_time_gap, p.w_link, p.w_pin}; }
-
-static int check_builder(const std::string &w, const sfc_builder *b) {
-    if (!b) return fail(SF_ERR_ARG, w + ": null builder");
-    if (!b->h) return fail(SF_ERR_STATE, w + ": the handle this builder was created from has been destroyed");
-    return SF_OK;
-}
-
-// (a builder's device memory is released with its handle's device current and its stream drained: sf_destroy)
-void orphan_builders(sf_handle *h) {
-    for (sfc_builder *b : h->builders) {
-        b->own.release_all();
-        b->blk.forget();
-        b->h = nullptr;
-    }
-    h->builders.clear();
-}
 
 extern "C" {
 
@@ -99,22 +82,17 @@ int sfc_link_sample(const float *sa, const float *so, float zA, float zO, const 
 
 int sfc_builder_create(sf_handle *h, sfc_builder **out) {
     if (!h || !out) return fail(SF_ERR_ARG, "sfc_builder_create: null argument");
-    if (!handle_alive(h)) return fail(SF_ERR_STATE, "sfc_builder_create: this handle has been destroyed");
+    if (int e = check_live_handle("sfc_builder_create", h)) return e;
     sfc_builder *b = new sfc_builder;
     b->h = h;
-    h->builders.push_back(b);
+    h->parts.enter(b);
     *out = b;
     return SF_OK;
 }
 
 void sfc_builder_destroy(sfc_builder *b) {
     if (!b) return;
-    if (sf_handle *h = b->h) {  // the handle is alive: its device, after its queued work
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        h->builders.erase(std::remove(h->builders.begin(), h->builders.end(), b), h->builders.end());
-        b->own.release_all();
-    }  // else: sf_destroy of the handle already released the memory and left the builder as an empty shell
+    part_destroy(b);
     delete b;
 }
 
@@ -122,7 +100,7 @@ void sfc_builder_destroy(sfc_builder *b) {
 int sfc_build(sfc_builder *b, int n, sf_map *const *maps_new, sf_map *const *maps_old, const sfv_view *views_from, const sfv_view *views_to,
               const sfc_params *params, sfc_record *out, int max_records, sfc_counts *counts_out) {
     const std::string w("sfc_build");
-    if (int e = check_builder(w, b)) return e;
+    if (int e = check_part("sfc_build", b, "builder")) return e;
     sf_handle *h = b->h;
     if (n < 0) return fail(SF_ERR_ARG, w + ": n < 0");
     if (2 * (long long)n > 65535) return fail(SF_ERR_ARG, w + ": more than 65535 views in one call (two per entry)");

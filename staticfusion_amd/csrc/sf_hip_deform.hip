@@ -25,11 +25,10 @@ static_assert(SFD_SOLVE_MAX_ITERATIONS == SFD_MAX_ITERATIONS && SFD_SOLVE_MAX_NO
                   SFD_SOLVE_DEGENERATE == SFD_DEGENERATE,
               "sf_deform_solve.h restates the constants of include/sf_deform.h");
 
-struct sfd_graph {
-    sf_handle *h = nullptr;  // null: the handle has been destroyed
+struct SF_INTERNAL sfd_graph : SfPart {
     int max_nodes = 0, G = 0;
     SfCallBlock blk;  // host copy 0: G x 4 floats (g, time), then G x 12 (M); host copy 1: the entry table of a call
-    SfOwner own;
+    void shelled() override { blk.forget(); }
 };
 
 static int check_params(const sfd_params *p) {
@@ -47,11 +46,7 @@ static int check_solve_params(const sfd_solve_params *p) {
     return SF_OK;
 }
 
-static int check_graph(const std::string &w, const sfd_graph *g) {
-    if (!g) return fail(SF_ERR_ARG, w + ": null graph");
-    if (!g->h) return fail(SF_ERR_STATE, w + ": the handle this graph was created from has been destroyed");
-    return SF_OK;
-}
+static int check_graph(const char *what, const sfd_graph *g) { return check_part(what, g, "graph"); }
 
 // the arguments of the pure-host calls that take a graph as arrays
 static int check_arrays(const std::string &w, int G, int max_G, const float *pos, const float *times, const float *M, bool need_M, float time_window) {
@@ -62,30 +57,20 @@ static int check_arrays(const std::string &w, int G, int max_G, const float *pos
     return SF_OK;
 }
 
-// (a graph's device memory is released with its handle's device current and its stream drained: sf_destroy)
-void orphan_graphs(sf_handle *h) {
-    for (sfd_graph *g : h->graphs) {
-        g->own.release_all();
-        g->blk.forget();
-        g->h = nullptr;
-    }
-    h->graphs.clear();
-}
-
 // sfd_bind_maps (apply false) and sfd_apply_maps: every check of the refusal list, then per distinct graph the layout of its
 // block, the growth of all of them, the uploads, one launch, the results.
 static int run(const char *what, bool apply, sf_handle *h, int n, sf_map *const *maps, sfd_graph *const *graphs, const sfd_params *params, int32_t *idx_out,
                float *w_out, sfd_counts *counts_out) {
     const std::string w(what);
     if (!h || n < 0) return fail(SF_ERR_ARG, w + ": bad argument");
-    if (!handle_alive(h)) return fail(SF_ERR_STATE, w + ": this handle has been destroyed");
+    if (int e = check_live_handle(w, h)) return e;
     if (n == 0) return SF_OK;
     if (int e = check_batch(w, n)) return e;
     if (!maps || !graphs || !params || (apply ? !counts_out : (!idx_out || !w_out))) return fail(SF_ERR_ARG, w + ": null argument");
     for (int q = 0; q < n; q++) {
         if (int e = check_map(what, h, maps[q])) return e;
         if (int e = check_distinct(w, maps, q, "the same map twice in one call")) return e;
-        if (int e = check_graph(w, graphs[q])) return e;
+        if (int e = check_graph(what, graphs[q])) return e;
         if (graphs[q]->h != h) return fail(SF_ERR_ARG, w + ": a graph of another handle");
         if (graphs[q]->G == 0) return fail(SF_ERR_STATE, w + ": a graph without nodes");
         if (int e = check_params(params + q)) return e;
@@ -210,24 +195,19 @@ int sfd_check_solve_params(const sfd_solve_params *p) { return check_solve_param
 
 int sfd_graph_create(sf_handle *h, int max_nodes, sfd_graph **out) {
     if (!h || !out) return fail(SF_ERR_ARG, "sfd_graph_create: null argument");
-    if (!handle_alive(h)) return fail(SF_ERR_STATE, "sfd_graph_create: this handle has been destroyed");
+    if (int e = check_live_handle("sfd_graph_create", h)) return e;
     if (max_nodes < 1 || max_nodes > SFD_MAX_NODES) return fail(SF_ERR_ARG, "sfd_graph_create: max_nodes lies in 1..1024");
     sfd_graph *g = new sfd_graph;
     g->h = h;
     g->max_nodes = max_nodes;
-    h->graphs.push_back(g);
+    h->parts.enter(g);
     *out = g;
     return SF_OK;
 }
 
 void sfd_graph_destroy(sfd_graph *g) {
     if (!g) return;
-    if (sf_handle *h = g->h) {  // the handle is alive: its device, after its queued work
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        h->graphs.erase(std::remove(h->graphs.begin(), h->graphs.end(), g), h->graphs.end());
-        g->own.release_all();
-    }  // else: sf_destroy of the handle already released the memory and left the graph as an empty shell
+    part_destroy(g);
     delete g;
 }
 

@@ -12,8 +12,7 @@ static_assert(sizeof(sfk_fern) == 16, "include/sf_keyframes.h: sfk_fern is 16 by
 static_assert(sizeof(sfk_match) == 8, "include/sf_keyframes.h: sfk_match is 8 bytes");
 static_assert(sizeof(sfk_info) == 48, "include/sf_keyframes.h: sfk_info is 48 bytes");
 
-struct sfk_db {
-    sf_handle *h = nullptr;  // null: the handle has been destroyed
+struct SF_INTERNAL sfk_db : SfPart {
     int rows = 0, cols = 0, cell = 0, gr = 0, gc = 0, n_ferns = 0, words = 0, capacity = 0, count = 0;
     sfk_fern *d_ferns = nullptr;
     uint32_t *d_codes = nullptr;  // [words][capacity]: word w of slot s at w * capacity + s
@@ -21,7 +20,12 @@ struct sfk_db {
     std::vector<float> poses;     // [count][16]
     std::vector<int32_t> stamps;  // [count]
     SfCallBlock scratch;          // what one call uploads, encodes and reads back; host copy 0: the frame table
-    SfOwner own;
+    void shelled() override {
+        scratch.forget();
+        d_ferns = nullptr;
+        d_codes = nullptr;
+        d_tags = nullptr;
+    }
 };
 
 static int check_ferns(const sfk_fern *ferns, int n_ferns, int n_cells) {
@@ -34,11 +38,7 @@ static int check_ferns(const sfk_fern *ferns, int n_ferns, int n_cells) {
     return SF_OK;
 }
 
-static int check_db(const char *what, const sfk_db *db) {
-    if (!db) return fail(SF_ERR_ARG, std::string(what) + ": null database");
-    if (!db->h) return fail(SF_ERR_STATE, std::string(what) + ": the handle this database was created from has been destroyed");
-    return SF_OK;
-}
+static int check_db(const char *what, const sfk_db *db) { return check_part(what, db, "database"); }
 
 static int check_streams(const char *what, const sfk_db *db, int n, const int32_t *streams) {
     const sf_handle *h = db->h;
@@ -208,15 +208,6 @@ static int query_or_add(const char *what, sfk_db *db, int n, const int32_t *stre
     return SF_OK;
 }
 
-// (a database's device memory is released with its handle's device current and its stream drained: sf_destroy)
-void orphan_keyframe_dbs(sf_handle *h) {
-    for (sfk_db *db : h->keyframe_dbs) {
-        db->own.release_all();
-        db->h = nullptr;
-    }
-    h->keyframe_dbs.clear();
-}
-
 extern "C" {
 
 int sfk_version(void) { return SFK_VERSION; }
@@ -265,19 +256,14 @@ int sfk_db_create(sf_handle *h, int rows, int cols, int cell, const sfk_fern *fe
         return e;
     }
     db->h = h;
-    h->keyframe_dbs.push_back(db);
+    h->parts.enter(db);
     *out = db;
     return SF_OK;
 }
 
 void sfk_db_destroy(sfk_db *db) {
     if (!db) return;
-    if (sf_handle *h = db->h) {  // the handle is alive: its device, after its queued work
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        h->keyframe_dbs.erase(std::remove(h->keyframe_dbs.begin(), h->keyframe_dbs.end(), db), h->keyframe_dbs.end());
-        db->own.release_all();
-    }  // else: sf_destroy of the handle already released the memory and left the database as an empty shell
+    part_destroy(db);
     delete db;
 }
 

@@ -174,7 +174,7 @@ int sfw_page_out(sf_map *m, const sfw_filter *f, float *surfels_out, int max_cou
 
 int sfw_append(sf_map *m, const float *surfels, int count) {
     if (!m || count < 0 || (!surfels && count > 0)) return fail(SF_ERR_ARG, "sfw_append: bad argument");
-    if (!m->h) return fail(SF_ERR_STATE, "sfw_append: the handle this map was created from has been destroyed");
+    if (int e = check_part("sfw_append", m, "map")) return e;
     if ((long long)count + m->count > (long long)m->capacity) return fail(SF_ERR_STATE, "sfw_append: count + the map's count exceeds its capacity");
     HIP_TRY(hipSetDevice(m->h->device));
     if (count) {

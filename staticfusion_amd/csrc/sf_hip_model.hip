@@ -63,8 +63,7 @@ void invert_pose(const float pose[16], float out[16]) {  // (shared: sf_host.h)
         for (int c = 0; c < 4; c++) out[r + 4 * c] = float(Ai[r * 4 + c]);
 }
 int check_map(const char *what, const sf_handle *h, const sf_map *m) {  // (shared: sf_host.h)
-    if (!m) return fail(SF_ERR_ARG, std::string(what) + ": null map");
-    if (!m->h) return fail(SF_ERR_STATE, std::string(what) + ": the handle this map was created from has been destroyed");
+    if (int e = check_part(what, m, "map")) return e;
     if (m->h != h) return fail(SF_ERR_ARG, std::string(what) + ": a map belongs to the handle it was created from");
     return SF_OK;
 }
@@ -263,49 +262,28 @@ int sf_map_create(sf_handle *h, int capacity, sf_map **out) {
         sf_map_destroy(m);
         return e;
     }
-    h->maps.push_back(m);
+    h->parts.enter(m);
     *out = m;
     return SF_OK;
 }
-// (a map's device memory is released with its handle's device current and its stream drained)
-void orphan_maps(sf_handle *h) {
-    for (sf_map *m : h->maps) {
-        m->own.release_all();
-        m->h = nullptr;
-    }
-    h->maps.clear();
-}
 void sf_map_destroy(sf_map *m) {
     if (!m) return;
-    if (sf_handle *h = m->h) {  // the handle is alive: its device, after its queued work
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        for (auto it = h->maps.begin(); it != h->maps.end(); ++it)
-            if (*it == m) {
-                h->maps.erase(it);
-                break;
-            }
-        m->own.release_all();
-    }  // else: sf_destroy of the handle already released the memory and left the map as an empty shell
+    part_destroy(m);
     delete m;
 }
 // include/sf_migrate.h: the map follows its stream to another handle. Its memory is its own (sf_map::own) and stays where it is;
 // what changes is whose stream orders the work on it and whose sf_destroy releases it.
 int sfm_map_rebind(sf_map *m, sf_handle *dst) {
     if (!m || !dst) return fail(SF_ERR_ARG, "sfm_map_rebind: null");
+    if (check_part("sfm_map_rebind", m, "map")) return SF_ERR_ARG;  // (the one call that answers a shell with this code)
     sf_handle *old = m->h;
-    if (!old) return fail(SF_ERR_ARG, "sfm_map_rebind: the handle this map was created from has been destroyed");
     if (old == dst) return SF_OK;
     if (dst->device != old->device) return fail(SF_ERR_ARG, "sfm_map_rebind: the destination handle is on another device");
     if (dst->k.rows != old->k.rows || dst->k.cols != old->k.cols) return fail(SF_ERR_ARG, "sfm_map_rebind: the destination handle has another resolution");
     HIP_TRY(hipSetDevice(old->device));
     HIP_TRY(hipStreamSynchronize(old->stream));  // nothing queued on the old handle still works on the map
-    for (auto it = old->maps.begin(); it != old->maps.end(); ++it)
-        if (*it == m) {
-            old->maps.erase(it);
-            break;
-        }
-    dst->maps.push_back(m);
+    old->parts.leave(m);
+    dst->parts.enter(m);
     m->h = dst;
     return SF_OK;
 }
@@ -485,7 +463,7 @@ int sf_map_info(sf_map *m, int *count, int *tick, float pose[16], int stats[4]) 
 }
 int sf_map_download(sf_map *m, float *surfels, int max_count) {
     if (!m || (!surfels && max_count > 0) || max_count < 0) return fail(SF_ERR_ARG, "bad argument");
-    if (!m->h) return fail(SF_ERR_STATE, "the handle this map was created from has been destroyed");
+    if (int e = check_part(nullptr, m, "map")) return e;
     const size_t k = (size_t)std::min(max_count, m->count);
     if (k) return d2h(m->h, surfels, m->buf[0], k * 12 * sizeof(float));
     return SF_OK;
@@ -493,7 +471,7 @@ int sf_map_download(sf_map *m, float *surfels, int max_count) {
 int sf_map_upload(sf_map *m, const float *surfels, int count, const float pose[16], int tick) {
     if (!m || (!surfels && count > 0) || count < 0 || !pose || tick < 1) return fail(SF_ERR_ARG, "bad argument");
     if (count > m->capacity) return fail(SF_ERR_ARG, "count exceeds the map's capacity");
-    if (!m->h) return fail(SF_ERR_STATE, "the handle this map was created from has been destroyed");
+    if (int e = check_part(nullptr, m, "map")) return e;
     HIP_TRY(hipSetDevice(m->h->device));
     if (count) {
         HIP_TRY(hipMemcpyAsync(m->buf[0], surfels, (size_t)count * 12 * sizeof(float), hipMemcpyHostToDevice, m->h->stream));
@@ -506,7 +484,7 @@ int sf_map_upload(sf_map *m, const float *surfels, int count, const float pose[1
 }
 int sf_map_get_index_map(sf_map *m, uint32_t *out) {
     if (!m || !out) return fail(SF_ERR_ARG, "null");
-    if (!m->h) return fail(SF_ERR_STATE, "the handle this map was created from has been destroyed");
+    if (int e = check_part(nullptr, m, "map")) return e;
     if (!m->have_index) return fail(SF_ERR_STATE, "no index map yet (sf_map_fuse_frame with tick > 1 renders it)");
     HIP_TRY(hipSetDevice(m->h->device));
     const size_t n = m->h->k.n0 * 16;

@@ -1,9 +1,9 @@
 // sf_hip_tracks.hip — libsf_hip.so, the interface of include/sf_tracks.h (symbols sft_*): the moving regions of
 // include/sf_regions.h followed from frame to frame (kernels: sf_tracks.h; the assignment: sf_track_assign.h). A tracker's
-// state -- per slot the head, the camera, the rows and the previous frame's clipped labels and depth -- is one block of the
-// handle, and its scratch -- the entry table, the records, summaries and label images of the labelling, the overlap tables
-// and, for the host forms, the uploaded frames and the outputs of a call -- a call block under the handle's owner
-// (sft_tracker::scratch; sf_call_block.h: layout, growth and lifetime).
+// state -- per slot the head, the camera, the rows and the previous frame's clipped labels and depth -- is one block, and
+// its scratch -- the entry table, the records, summaries and label images of the labelling, the overlap tables and, for the
+// host forms, the uploaded frames and the outputs of a call -- a call block (sft_tracker::scratch; sf_call_block.h: layout,
+// growth and lifetime), both under the tracker's own owner, as a keyframe database has one (sf_parts.h).
 // The labelling is sfr_label_images_device as it is: its own scratch is the handle's regions block. What the host keeps per
 // slot is what it handed in itself: whether the slot holds a previous frame, and that frame's camera.
 #include "../../include/sf_tracks.h"
@@ -18,15 +18,18 @@ static_assert(sizeof(sft_summary) == 32, "include/sf_tracks.h: sft_summary is 32
 static_assert(sizeof(sft_info) == 32 && sizeof(sft_slot) == 16, "include/sf_tracks.h: sft_info is 32 bytes, sft_slot 16");
 static_assert(sizeof(TkSlotHead) == 64 && SFT_MAX_TRACKS == SFT_NT && SFT_PB % SFT_NT == 0, "sf_tracks.h: one lane per row of the assignment");
 
-struct sft_tracker {
-    sf_handle *h = nullptr;  // null: the handle has been destroyed
+struct SF_INTERNAL sft_tracker : SfPart {
     int rows = 0, cols = 0, n_slots = 0, max_tracks = 0;
     TkLayout lay{};
     unsigned char *state = nullptr;    // n_slots * lay.stride bytes (zero-filled: every slot is fresh)
     SfCallBlock scratch;               // what one call uploads, computes and reads back (host copy 0: the entry table of an
-                                       // update, host copy 1: the slots of a reset); a block of the handle's owner
+                                       // update, host copy 1: the slots of a reset)
     std::vector<unsigned char> has_prev;  // per slot: it holds a previous frame
     std::vector<sft_camera> cams;         // per slot: that frame's camera
+    void shelled() override {
+        state = nullptr;
+        scratch.forget();
+    }
 };
 
 static int check_track_params(const sft_params *p) {
@@ -63,11 +66,7 @@ static int relative(const float *p0, const float *p1, float *D) {
     return SF_OK;
 }
 
-static int check_tracker(const char *what, const sft_tracker *t) {
-    if (!t) return fail(SF_ERR_ARG, std::string(what) + ": null tracker");
-    if (!t->h) return fail(SF_ERR_STATE, std::string(what) + ": the handle this tracker was created from has been destroyed");
-    return SF_OK;
-}
+static int check_tracker(const char *what, const sft_tracker *t) { return check_part(what, t, "tracker"); }
 
 static TkLayout slot_layout(int rows, int cols, int max_tracks) {
     SfPlan p;
@@ -142,7 +141,7 @@ static int update(const char *what, CallForm form, sft_tracker *t, int rows, int
             if (ids && ids[q]) o_ids[(size_t)q] = p.take(px * 4);
         }
     }
-    if (int e = t->scratch.grow(h->own, p.off, h->stream)) return e;
+    if (int e = t->scratch.grow(t->own, p.off, h->stream)) return e;
     unsigned char *base = t->scratch.dev;
     // ---- the frames, and the labelling as sf_regions.h has it: labels, summaries and records into the scratch
     std::vector<const void *> dp((size_t)n), bp((size_t)n);
@@ -222,16 +221,6 @@ static int update(const char *what, CallForm form, sft_tracker *t, int rows, int
     return SF_OK;
 }
 
-// (a tracker's blocks are the handle's: sf_destroy releases them with everything else of the handle)
-void orphan_trackers(sf_handle *h) {
-    for (sft_tracker *t : h->trackers) {
-        t->state = nullptr;
-        t->scratch.forget();
-        t->h = nullptr;
-    }
-    h->trackers.clear();
-}
-
 extern "C" {
 
 int sft_version(void) { return SFT_VERSION; }
@@ -280,27 +269,21 @@ int sft_tracker_create(sf_handle *h, int rows, int cols, int n_slots, int max_tr
     sft_tracker *t = new sft_tracker;
     t->rows = rows; t->cols = cols; t->n_slots = n_slots; t->max_tracks = max_tracks;
     t->lay = slot_layout(rows, cols, max_tracks);
-    if (int e = dev_alloc(h, &t->state, (size_t)n_slots * t->lay.stride)) {
+    if (int e = t->own.device(&t->state, (size_t)n_slots * t->lay.stride)) {
         delete t;
         return e;
     }
     t->has_prev.assign((size_t)n_slots, 0);
     t->cams.assign((size_t)n_slots, sft_camera{});
     t->h = h;
-    h->trackers.push_back(t);
+    h->parts.enter(t);
     *out = t;
     return SF_OK;
 }
 
 void sft_tracker_destroy(sft_tracker *t) {
     if (!t) return;
-    if (sf_handle *h = t->h) {  // the handle is alive: its device, after its queued work
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        h->trackers.erase(std::remove(h->trackers.begin(), h->trackers.end(), t), h->trackers.end());
-        h->own.free_device(t->state);
-        h->own.free_device(t->scratch.dev);
-    }  // else: sf_destroy of the handle already released the memory and left the tracker as an empty shell
+    part_destroy(t);
     delete t;
 }
 
@@ -332,7 +315,7 @@ int sft_reset_slots(sft_tracker *t, int n, const int32_t *slots, int restart_ids
         if (slots[q] < 0 || slots[q] >= t->n_slots) return fail(SF_ERR_ARG, "sft_reset_slots: slot out of range");
     sf_handle *h = t->h;
     HIP_TRY(hipSetDevice(h->device));
-    if (int e = t->scratch.grow(h->own, (size_t)n * 4, h->stream)) return e;
+    if (int e = t->scratch.grow(t->own, (size_t)n * 4, h->stream)) return e;
     int32_t *stab = t->scratch.resized<int32_t>((size_t)n, 1);
     std::memcpy(stab, slots, (size_t)n * 4);
     if (int e = t->scratch.upload(0, stab, (size_t)n * 4, h->stream)) return e;

@@ -5,7 +5,10 @@
 //                      (SfOwner::grow, here dev_grow) and the ring of per-call tables (SfRing); host only, no kernel
 //   sf_call_block.h    the per-call block of a companion interface: its layout rule (SfPlan), the block with the host copies
 //                      of its tables (SfCallBlock) and the rules of their lifetime; host only, no kernel
-//   sf_hip.hip         handle lifetime, parameters, the builds of the frame kernel, launch()
+//   sf_parts.h         what is created from a handle and may outlive it (maps, keyframe databases, trackers, deformation
+//                      graphs, closure builders): their base (SfPart), the handle's list of them (SfParts) and the rules of
+//                      their lifetime; host only, no kernel
+//   sf_hip.hip         handle lifetime and the list of live handles, parameters, the builds of the frame kernel, launch()
 //   sf_hip_solver.hip  images in, frames (one or several per launch), results and debug planes out, measurement support
 //   sf_hip_input.hip   the input stage: loader decimation / RGB -> intensity, bilateral depth filter (sf_input.h)
 //   sf_hip_model.hip   frame-to-model prediction and the surfel map without OpenGL (sf_predict.h, sf_fusion.h); the map
@@ -30,7 +33,7 @@
 //   sf_hip_tracks.hip  region tracks: the moving regions followed from frame to frame, with a metric box (sf_tracks.h,
 //                      sf_track_assign.h; its interface is include/sf_tracks.h, symbols sft_*)
 //   sf_hip_bodies.hip  region motion: the rigid motion of every moving region between two frames (sf_bodies.h,
-//                      sf_body_world.h; its interface is include/sf_bodies.h, symbols sfb_*); the list of live handles
+//                      sf_body_world.h; its interface is include/sf_bodies.h, symbols sfb_*)
 //   sf_hip_body_maps.hip  body maps: every moving region fused into a surfel map of its own (sf_body_maps.h,
 //                      sf_body_map_rules.h; its interface is include/sf_body_maps.h, symbols sfp_*)
 //   sf_hip_deform.hip  deformation graphs: maps bent by the nodes of a graph, and the solver for their transforms
@@ -50,7 +53,7 @@
 
 #include "sf_cluster.h"
 #include "sf_device_common.h"
-#include "sf_call_block.h"  // SfPlan, SfCallBlock; sf_resources.h: SF_INTERNAL, sf_fail, SfOwner, SfRing
+#include "sf_parts.h"  // SfPart, SfParts; sf_call_block.h: SfPlan, SfCallBlock; sf_resources.h: SF_INTERNAL, sf_fail, SfOwner, SfRing
 
 // the two builds of the frame kernels (sf_frame_kernels.hip, -DSF_NT=256 / -DSF_NT=1024)
 struct FrameVariant {
@@ -70,7 +73,7 @@ struct sf_handle {
     int *d_order = nullptr;   // KArgs::order storage (more streams than resident workgroups: a launch has a tail)
     int max_blocks_o5 = 0;  // throughput build: resident workgroups of the 5-per-CU kernel (0: not used)
     const FrameVariant *fv = nullptr;  // set by sf_create_ex
-    std::vector<struct sf_map *> maps;  // live maps created from this handle: sf_destroy releases their memory and orphans them
+    SfParts parts;  // what was created from this handle and lives: maps, keyframe databases, trackers, graphs, builders (sf_parts.h)
     bool reforder = false;  // the library's frame kernels are the reference-order build (sf_reforder.h)
     int cluster_grid = 0;  // SF_VARIANT_CLUSTER: blocks per launch (8 XCDs x streams per XCD x workgroups per stream)
     hipStream_t own_stream = nullptr;
@@ -140,19 +143,10 @@ struct sf_handle {
     SfCallBlock join;       // sf_hip_join.hip
     SfCallBlock bodies;     // sf_hip_bodies.hip: host copy 0 the entry table, host copy 1 the pair table
     SfCallBlock body_maps;  // sf_hip_body_maps.hip
-    // live keyframe databases and trackers created from this handle (sf_hip_keyframes.hip, sf_hip_tracks.hip): sf_destroy
-    // releases their memory and orphans them, like the maps. A tracker's blocks are blocks of `own`, a database has an owner.
-    std::vector<struct sfk_db *> keyframe_dbs;
-    std::vector<struct sft_tracker *> trackers;
-    // and its deformation graphs (sf_hip_deform.hip): each owns its call block through an owner of its own, like a database
-    std::vector<struct sfd_graph *> graphs;
-    // and its closure builders (sf_hip_closure.hip), each with its call block under an owner of its own likewise
-    std::vector<struct sfc_builder *> builders;
 };
 
 // the surfel map (sf_hip_model.hip creates, fuses and releases it; sf_hip_map_window.hip partitions it)
-struct sf_map {
-    sf_handle *h = nullptr;
+struct SF_INTERNAL sf_map : SfPart {  // (own: the map's device blocks, not zero-filled)
     int capacity = 0;
     float *buf[2] = {nullptr, nullptr};  // the model lives in buf[0] between calls; buf[1] holds the merged model inside a fuse
     int count = 0, tick = 1;
@@ -165,7 +159,13 @@ struct sf_map {
     int *block_counts = nullptr;
     bool have_index = false;
     int epoch = 0;  // index images rendered since the key image was last filled with ones; tag = 255 - epoch
-    SfOwner own;    // the map's device blocks (not zero-filled): released by sf_map_destroy, or by its handle's sf_destroy
+    void shelled() override {
+        buf[0] = buf[1] = rec = nullptr;
+        keys = occ = nullptr;
+        winner = meta = index_export = nullptr;
+        flags = nullptr;
+        block_counts = nullptr;
+    }
 };
 
 // Constructor state of a stream (reference FrontEnd.cpp:79-81,110,152-154), as the 32-bit word at byte offset `off` of its
@@ -278,22 +278,36 @@ SF_INTERNAL int sfv_draw_keys(sf_handle *h, const ViewPlan &p, const ViewJob *jo
 struct WindowArgs;  // sf_window_args.h
 SF_INTERNAL void sfw_launch_scan(sf_handle *h, const WindowArgs *d_tab, int n);
 SF_INTERNAL void sfw_launch_write(sf_handle *h, const WindowArgs *d_tab, unsigned blocks, int n);
-SF_INTERNAL void orphan_keyframe_dbs(sf_handle *h);  // sf_hip_keyframes.hip: sf_destroy releases the handle's keyframe databases
-SF_INTERNAL void orphan_trackers(sf_handle *h);      // sf_hip_tracks.hip: sf_destroy leaves the handle's trackers as shells
-SF_INTERNAL void orphan_graphs(sf_handle *h);        // sf_hip_deform.hip: sf_destroy releases the handle's deformation graphs
-SF_INTERNAL void orphan_builders(sf_handle *h);      // sf_hip_closure.hip: sf_destroy releases the handle's closure builders
-// sf_hip_bodies.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the region
-// motion calls and the body map calls refuse a destroyed handle
-SF_INTERNAL void handle_born(const sf_handle *h);
-SF_INTERNAL void handle_gone(const sf_handle *h);
+// sf_hip.hip: the list of live handles (sf_create_ex enters a handle, sf_destroy takes it out), by which the calls that take
+// a handle and no part of it refuse one that is gone
 SF_INTERNAL bool handle_alive(const sf_handle *h);
+static inline int check_live_handle(const std::string &where, const sf_handle *h) {
+    if (!handle_alive(h)) return fail(SF_ERR_STATE, where + ": this handle has been destroyed");
+    return SF_OK;
+}
+// ---- the parts of a handle (sf_parts.h: the rules). The two refusals every call on a part begins with: `where` is the
+// caller's name, or null for the map calls whose refusals carry none; `noun` is what the part is called.
+static inline int check_part(const char *where, const SfPart *p, const char *noun) {
+    const std::string w = where ? std::string(where) + ": " : std::string();
+    if (!p) return fail(SF_ERR_ARG, w + "null " + noun);
+    if (!p->h) return fail(SF_ERR_STATE, w + "the handle this " + noun + " was created from has been destroyed");
+    return SF_OK;
+}
+// the part goes before its handle: the handle's device, after its queued work (a shell: nothing). The caller deletes it.
+static inline void part_destroy(SfPart *p) {
+    sf_handle *h = p->h;
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->parts.leave(p);
+    p->own.release_all();
+}
 extern "C" {  // (defined inside the extern "C" blocks of their files)
 SF_INTERNAL int check_stream(const sf_handle *h, int stream);                 // sf_hip.hip
 SF_INTERNAL int d2h(sf_handle *h, void *dst, const void *src, size_t bytes);  // sf_hip_solver.hip: drain the handle's stream, then copy
 SF_INTERNAL int input_alloc(sf_handle *h);                                    // sf_hip_input.hip: buffers of the input stage, on first use
-SF_INTERNAL void orphan_maps(sf_handle *h);                                   // sf_hip_model.hip: sf_destroy releases the handle's maps
 SF_INTERNAL void invert_pose(const float pose[16], float out[16]);            // sf_hip_model.hip: t_inv of the prediction, the fusion and the views
-// sf_hip_model.hip: a map handed to `what` beside h is not null (SF_ERR_ARG), not orphaned (SF_ERR_STATE) and h's own (SF_ERR_ARG)
+// sf_hip_model.hip: a map handed to `what` beside h is not null (SF_ERR_ARG), not a shell (SF_ERR_STATE) and h's own (SF_ERR_ARG)
 SF_INTERNAL int check_map(const char *what, const sf_handle *h, const sf_map *m);
 // sf_hip_model.hip: the table of a batched launch into h->tab_dev (grown on demand; it stays there for later launches of the call)
 SF_INTERNAL int upload_table(sf_handle *h, const void *src, size_t bytes, void **dev);

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
-from ._companion import binder, map_array, one_solver
+from ._companion import HandleChild, binder, map_array, one_solver
 
 _H = C.c_void_p
 _pp = C.POINTER(C.c_void_p)
@@ -168,25 +168,14 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(_fp)
 
 
-class Graph:
+class Graph(HandleChild):
     """one sfd_graph on a solver's handle: `set(pos, times, M=None)`, `get()`, `info()`, `close()`"""
 
+    _ptr, _destroy = "g", "graph_destroy"
+
     def __init__(self, solver, max_nodes=MAX_NODES):
-        self.solver, self.api = solver, solver.api
-        self.b = _bind(solver.api)
-        self.g = C.c_void_p()
+        super().__init__(solver, _bind(solver.api))
         self.b.check(self.b.graph_create(solver.h, int(max_nodes), C.byref(self.g)), "graph_create")
-
-    def close(self):
-        if self.g:
-            self.b.graph_destroy(self.g)
-            self.g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         i = SfdInfo()

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
-from ._companion import binder, ptr_array
+from ._companion import HandleChild, binder, ptr_array
 
 _H = C.c_void_p
 _pp = C.POINTER(C.c_void_p)
@@ -86,33 +86,22 @@ def _ip_(a):
     return a.ctypes.data_as(_ip)
 
 
-class KeyframeDb:
+class KeyframeDb(HandleChild):
     """numpy wrapper over one sfk_db: the keyframes of a solver's streams (or of images of any one size)"""
+
+    _ptr, _destroy = "db", "db_destroy"
 
     def __init__(self, solver, cell, ferns=None, n_ferns=128, seed=20261020, capacity=1024, rows=None, cols=None):
         """ferns: records of FERN_DTYPE, or None for default_ferns(n_ferns, seed, cells of the grid); rows, cols: the
         solver's unless given (the stream forms need the solver's)"""
-        self.solver, self.api = solver, solver.api
-        self.b = _bind(solver.api)
+        super().__init__(solver, _bind(solver.api))
         self.rows, self.cols = int(solver.rows if rows is None else rows), int(solver.cols if cols is None else cols)
         if ferns is None:
             ferns = default_ferns(n_ferns, seed, max((self.rows // max(cell, 1)) * (self.cols // max(cell, 1)), 1))
         self.ferns = np.ascontiguousarray(ferns, FERN_DTYPE).copy()
-        self.db = C.c_void_p()
         self.b.check(self.b.db_create(solver.h, self.rows, self.cols, int(cell), self.ferns.ctypes.data, self.ferns.shape[0], int(capacity), C.byref(self.db)),
                      "db_create")
         self.words = (self.ferns.shape[0] + 7) // 8
-
-    def close(self):
-        if self.db:
-            self.b.db_destroy(self.db)
-            self.db = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         rec = np.zeros(1, INFO_DTYPE)

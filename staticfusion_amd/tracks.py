@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import SfError
-from ._companion import binder, ptr_array
+from ._companion import HandleChild, binder, ptr_array
 from .regions import Params as RegionParams
 from .regions import SfrParams
 
@@ -155,28 +155,17 @@ def _list(x, n, kind, what):
     return x
 
 
-class Tracker:
+class Tracker(HandleChild):
     """numpy wrapper over one sft_tracker: n_slots followed cameras of one image size, at most max_tracks tracks each"""
+
+    _ptr, _destroy = "t", "tracker_destroy"
 
     def __init__(self, solver, n_slots=1, max_tracks=32, rows=None, cols=None):
         """rows, cols: the solver's unless given (the stream form needs the solver's)"""
-        self.solver, self.api = solver, solver.api
-        self.b = _bind(solver.api)
+        super().__init__(solver, _bind(solver.api))
         self.rows, self.cols = int(solver.rows if rows is None else rows), int(solver.cols if cols is None else cols)
         self.n_slots, self.max_tracks = int(n_slots), int(max_tracks)
-        self.t = C.c_void_p()
         self.b.check(self.b.tracker_create(solver.h, self.rows, self.cols, self.n_slots, self.max_tracks, C.byref(self.t)), "tracker_create")
-
-    def close(self):
-        if self.t:
-            self.b.tracker_destroy(self.t)
-            self.t = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         rec = np.zeros(1, INFO_DTYPE)

@@ -1,6 +1,7 @@
-// The host-side resource owner (staticfusion_amd/csrc/sf_resources.h: SfOwner, its growth rule, SfRing) and the per-call block
-// of the companion interfaces (sf_call_block.h: SfPlan, SfCallBlock) played through on the CPU. Stand-alone: the HIP functions the header calls are defined HERE -- malloc-backed, with a set of live pointers (a free
-// of an unknown one aborts), a log of calls and "fail the k-th acquiring call" --, and so is sf_fail. No HIP runtime, no
+// The host-side resource owner (staticfusion_amd/csrc/sf_resources.h: SfOwner, its growth rule, SfRing), the per-call block
+// of the companion interfaces (sf_call_block.h: SfPlan, SfCallBlock) and the lifetime of what is created from a handle
+// (sf_parts.h: SfPart, SfParts) played through on the CPU. Stand-alone: the HIP functions the headers call are defined HERE --
+// malloc-backed, with a set of live pointers (a free of an unknown one aborts), a log of calls and "fail the k-th acquiring call" --, and so is sf_fail. No HIP runtime, no
 // library. tests/test_host_resources_cpu.py compiles it with -fsanitize=address,undefined and runs it as a child process: once
 // without a failure, then once for every acquiring call of that run failing. It prints "ok <runs>" and returns 0, or names
 // the first failure and returns 1. What is still allocated at exit is LeakSanitizer's to report.
@@ -8,10 +9,10 @@
 #include <cstdlib>
 #include <map>
 
-#include "../../staticfusion_amd/csrc/sf_call_block.h"  // (includes sf_resources.h)
+#include "../../staticfusion_amd/csrc/sf_parts.h"  // (includes sf_call_block.h, which includes sf_resources.h)
 
 // ---- the HIP runtime of this program ---------------------------------------------------------------------------------
-enum Op { MALLOC, FREE, HOST_MALLOC, HOST_FREE, EVENT_CREATE, EVENT_DESTROY, STREAM_CREATE, STREAM_DESTROY, STREAM_SYNC, EVENT_SYNC, EVENT_RECORD, MEMCPY, MEMSET };
+enum Op { MALLOC, FREE, HOST_MALLOC, HOST_FREE, EVENT_CREATE, EVENT_DESTROY, STREAM_CREATE, STREAM_DESTROY, STREAM_SYNC, EVENT_SYNC, EVENT_RECORD, MEMCPY, MEMSET, SET_DEVICE };
 struct Call {
     Op op;
     const void *p;
@@ -79,6 +80,10 @@ hipError_t hipMemset(void *p, int v, size_t bytes) {
     must_be_live(p, MALLOC);
     std::memset(p, v, bytes);
     calls.push_back({MEMSET, p});
+    return hipSuccess;
+}
+hipError_t hipSetDevice(int) {
+    calls.push_back({SET_DEVICE, nullptr});
     return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t s) {
@@ -237,6 +242,127 @@ static bool ring_consistent(const Ring &r, int n) {
     for (int q = 0; q < n; q++)
         if (r.made(q) ? !(r.host[q] && r.dev[q] && r.event[q]) : (r.host[q] || r.dev[q] || r.event[q])) return false;
     return true;
+}
+
+// ---- a handle and its parts in miniature (sf_parts.h). The handle has what part_destroy of sf_host.h reads; a part has two
+// blocks and a call block under its own owner, like a keyframe database.
+struct SF_INTERNAL sf_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    SfOwner own;
+    SfParts parts;
+};
+struct SF_INTERNAL MiniPart : SfPart {
+    float *a = nullptr, *b = nullptr;
+    SfCallBlock blk;
+    int hooks = 0;
+    bool hook_in_order = false;
+    void shelled() override {  // (orphan_all: the owner has released, h is still set)
+        hooks++;
+        hook_in_order = own.dev.empty() && h != nullptr;
+        a = b = nullptr;
+        blk.forget();
+    }
+};
+static int part_create(sf_handle &h, bool enter, MiniPart **out) {  // (enter false: a create call that fails after h is set)
+    MiniPart *p = new MiniPart;
+    int e = p->own.device(&p->a, 100);
+    if (!e) e = p->own.device(&p->b, 50, false);
+    if (e) {
+        delete p;  // (its owner releases what it had)
+        return e;
+    }
+    p->h = &h;
+    if (enter) h.parts.enter(p);
+    *out = p;
+    return SF_OK;
+}
+static void part_destroy(SfPart *p) {  // as sf_host.h has it
+    sf_handle *h = p->h;
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->parts.leave(p);
+    p->own.release_all();
+}
+static bool is_shell(const MiniPart *p) { return !p->h && !p->a && !p->b && !p->blk.dev && !p->blk.bytes && p->own.dev.empty() && p->hooks == 1 && p->hook_in_order; }
+
+static int parts_scenario() {
+    sf_handle A, B;
+    for (sf_handle *h : {&A, &B})
+        if (step([&] { return h->stream ? SF_OK : h->own.stream(&h->stream, hipStreamDefault); }, [&] { return h->stream == nullptr; })) return 1;
+    const size_t n_streams = live.size();
+
+    // ---- five parts under their own owners, one with a call block that was outgrown once: the handle goes first
+    MiniPart *p[5] = {};
+    for (int q = 0; q < 5; q++) {
+        const size_t n_live = live.size();
+        if (step([&] { return p[q] ? SF_OK : part_create(A, true, &p[q]); }, [&] { return !p[q] && live.size() == n_live && A.parts.list.size() == (size_t)q; })) return 1;
+        CHECK(p[q]->h == &A && A.parts.list.size() == (size_t)q + 1 && A.parts.list.back() == p[q] && live.size() == n_live + 2);
+    }
+    for (size_t need : {3000, 9000}) {
+        unsigned char *const dev0 = p[2]->blk.dev;
+        if (step([&] { return p[2]->blk.grow(p[2]->own, need, A.stream); }, [&] { return p[2]->blk.dev == dev0; })) return 1;
+    }
+    CHECK(live.size() == n_streams + 11 && A.own.dev.empty());  // nothing of a part is the handle's
+    std::vector<const void *> blocks;
+    for (const auto &kv : live)
+        if (kv.second == MALLOC) blocks.push_back(kv.first);
+    size_t mark = calls.size();
+    A.parts.orphan_all();
+    CHECK(live.size() == n_streams && A.parts.list.empty() && count_op(mark, FREE) == 11 && calls.size() == mark + 11);
+    for (const void *b : blocks) CHECK(count_op(mark, FREE, b) == 1);
+    for (int q = 0; q < 5; q++) CHECK(is_shell(p[q]));
+    A.parts.orphan_all();  // (an empty list: nothing)
+    CHECK(calls.size() == mark + 11);
+    // ---- a shell destroyed afterwards touches no HIP function
+    mark = calls.size();
+    for (int q = 0; q < 5; q++) {
+        part_destroy(p[q]);
+        delete p[q];
+    }
+    CHECK(calls.size() == mark);
+
+    // ---- the part goes first: leave, release; orphan_all then frees nothing twice and leaves it alone
+    MiniPart *first = nullptr, *stays = nullptr;
+    if (step([&] { return first ? SF_OK : part_create(A, true, &first); }, [&] { return !first && A.parts.list.empty(); })) return 1;
+    if (step([&] { return stays ? SF_OK : part_create(A, true, &stays); }, [&] { return !stays && A.parts.list.size() == 1; })) return 1;
+    const void *const fa = first->a, *const fb = first->b;
+    mark = calls.size();
+    part_destroy(first);
+    CHECK(calls[mark].op == SET_DEVICE && calls[mark + 1].op == STREAM_SYNC && calls[mark + 1].p == A.stream);  // the handle's device, after its queued work
+    CHECK(find_op(mark, FREE, fa) > (long)mark + 1 && count_op(mark, FREE) == 2 && A.parts.list.size() == 1 && A.parts.list[0] == stays);
+    A.parts.orphan_all();
+    CHECK(count_op(mark, FREE, fa) == 1 && count_op(mark, FREE, fb) == 1 && first->hooks == 0 && first->h == &A && is_shell(stays));
+    delete first;
+    delete stays;
+    CHECK(live.size() == n_streams);
+
+    // ---- leave of a part that was never entered is harmless; so is the destroy of one that has h set and was not entered
+    MiniPart *entered = nullptr, *half = nullptr;
+    if (step([&] { return entered ? SF_OK : part_create(A, true, &entered); }, [&] { return !entered && A.parts.list.empty(); })) return 1;
+    if (step([&] { return half ? SF_OK : part_create(A, false, &half); }, [&] { return !half && A.parts.list.size() == 1; })) return 1;
+    A.parts.leave(half);
+    CHECK(A.parts.list.size() == 1 && A.parts.list[0] == entered && live.size() == n_streams + 4);
+    part_destroy(half);
+    delete half;
+    CHECK(A.parts.list.size() == 1 && A.parts.list[0] == entered && live.size() == n_streams + 2);
+
+    // ---- rebind: the part leaves A and enters B; orphaning A leaves it alone, orphaning B makes it a shell
+    A.parts.leave(entered);
+    B.parts.enter(entered);
+    entered->h = &B;
+    mark = calls.size();
+    A.parts.orphan_all();
+    CHECK(calls.size() == mark && entered->h == &B && entered->a && entered->hooks == 0 && live.size() == n_streams + 2);
+    entered->a[99] = 1.f;  // (still memory)
+    B.parts.orphan_all();
+    CHECK(is_shell(entered) && B.parts.list.empty() && live.size() == n_streams);
+    mark = calls.size();
+    part_destroy(entered);
+    delete entered;
+    CHECK(calls.size() == mark);
+    return 0;
 }
 
 static int scenario(int failing, int *acquiring_calls) {
@@ -411,6 +537,8 @@ static int scenario(int failing, int *acquiring_calls) {
         CHECK(live.empty());
         CHECK(m.own.dev.empty() && m.own.pinned.empty() && m.own.events.empty() && m.own.streams.empty());
     }  // (the destructor of an owner that has released everything does nothing: a second free would abort above)
+    CHECK(live.empty());
+    if (parts_scenario()) return 1;  // (its two handles release their streams on the way out)
     CHECK(live.empty());
     CHECK(failing == 0 || fired);
     *acquiring_calls = acquired;

@@ -39,6 +39,8 @@ def test_header_table_and_exports_name_the_same_functions():
         out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
         assert sorted(set(re.findall(r" T (sfc_\w+)", out))) == names, lib
         assert "sfc_link_core" not in out and "orphan_builders" not in out, "the shared text is not exported"
+        # ... nor what orphans a builder now (sf_parts.h, sf_host.h), nor the builder's own hook and type
+        assert not re.search(r"SfPart|shelled|orphan_all|part_destroy|check_part|check_live_handle|_ZT[VIS]\d+sfc_builder", out), lib
     # a companion of the ABI, not a part of it; no other header or binding names sfc_*
     for path in glob.glob(os.path.join(ROOT, "include", "*")):
         if os.path.basename(path) != "sf_closure.h":

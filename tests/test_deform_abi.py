@@ -40,6 +40,8 @@ def test_header_table_and_exports_name_the_same_functions():
         out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
         assert sorted(set(re.findall(r" T (sfd_\w+)", out))) == names, lib
         assert "sfd_bind_core" not in out and "sfd_solve_core" not in out and "orphan_graphs" not in out, "the shared text is not exported"
+        # ... nor what orphans a graph now (sf_parts.h, sf_host.h), nor the graph's own hook and type
+        assert not re.search(r"SfPart|shelled|orphan_all|part_destroy|check_part|check_live_handle|_ZT[VIS]\d+sfd_graph", out), lib
     # a companion of the ABI, not a part of it; no other header or binding names sfd_*, and this header and its binding name
     # none of the prefixes the other ABI tests search every header and every binding for, nor the oracle's
     for path in glob.glob(os.path.join(ROOT, "include", "*")):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, driver_params, hip_runtime, make_solver
-from staticfusion_amd import SfError, SurfelMap, map_window, score, streams, view
+from staticfusion_amd import SfError, SurfelMap, closure, deform, keyframes, map_window, score, streams, tracks, view
 from staticfusion_amd.synth import make_sequence
 
 pytestmark = pytest.mark.gpu
@@ -168,3 +168,92 @@ def test_release_with_work_outstanding(hip_auto, golden, pair):
     assert m.info()["count"] > 0 and np.isfinite(fresh.T(0)).all() and not np.array_equal(fresh.T(0), np.eye(4))
     m.close()
     fresh.close()
+
+
+# ---- the five kinds of part of a handle (csrc/sf_parts.h): a map, a keyframe database, a tracker, a deformation graph, a closure builder
+SENT = -77
+
+
+def five_parts(s):
+    return SurfelMap(s), keyframes.KeyframeDb(s, 5, n_ferns=32), tracks.Tracker(s, 1, 4), deform.Graph(s, 4), closure.Builder(s)
+
+
+def camera(s):
+    return tracks.Camera(np.eye(4), 0.5 * (s.cols - 1), 0.5 * (s.rows - 1), 0.5 * s.cols, 0.5 * s.cols)
+
+
+def use_each_once(s, g, parts):
+    """every part used once, so that it holds device memory and a grown call block; everything the five calls return"""
+    m, db, t, gr, bld = parts
+    load(s, g, 0)
+    m.fuse_frame(0, None)  # a fuse into the map
+    out = [m.download(), np.array(m.info()["stats"])]
+    out += [db.add_streams([0], [np.eye(4)], [0]), db.get()["codes"]]  # one keyframe added to the database
+    summ, per = t.update_streams([0], [0], [camera(s)])  # one tracker update
+    out += [summ, per[0]]
+    nodes = out[0][:: max(out[0].shape[0] // 4, 1)][:4]
+    gr.set(nodes[:, 0:3], nodes[:, 6])  # a graph of 4 nodes set ...
+    idx, w = deform.bind_maps([m], gr)[0]  # ... and bound
+    out += [idx, w]
+    v = view.default_view(s, m)
+    recs, counts = bld.build([m], [m], [v], [v], closure.Params(stride=4))  # one closure build at stride 4
+    out += [recs, np.array([counts[0][k] for k in sorted(counts[0])])]
+    assert out[0].shape[0] > 4 and gr.info()["n_nodes"] == 4 and db.info()["count"] == 1 and counts[0]["n_samples"] > 0 and idx.shape == (out[0].shape[0], 4)
+    return out
+
+
+def refused_with_sentinels(s, parts, v):
+    """after sf_destroy of the handle: one call per part answers SF_ERR_STATE (-3) and writes nothing (v: a view made before)"""
+    m, db, t, gr, bld = parts
+    fp = C.POINTER(C.c_float)
+    buf = np.full((4, 12), SENT, np.float32)
+    assert s.api.map_download(m.m, buf.ctypes.data_as(fp), 4) == -3 and (buf == SENT).all()
+    one, pose, slots = (C.c_int32 * 1)(0), np.eye(4, dtype=np.float32).ravel(), np.full(1, SENT, np.int32)
+    assert db.b.add_streams(db.db, 1, one, pose.ctypes.data, one, one, 0, slots.ctypes.data, None) == -3 and (slots == SENT).all()
+    summ, trk = np.full(1, SENT, tracks.SUMMARY_DTYPE), np.full(4, SENT, tracks.TRACK_DTYPE)
+    code = t.b.update_streams(t.t, 1, one, one, (tracks.SftCamera * 1)(camera(s)), (tracks.SfrParams * 1)(tracks.RegionParams()), (tracks.SftParams * 1)(tracks.Params()),
+                              summ.ctypes.data, trk.ctypes.data, None)
+    assert code == -3 and (summ == np.full(1, SENT, tracks.SUMMARY_DTYPE)).all() and (trk == np.full(4, SENT, tracks.TRACK_DTYPE)).all()
+    pos, times, M = np.full((4, 3), SENT, np.float32), np.full(4, SENT, np.float32), np.full((4, 12), SENT, np.float32)
+    assert gr.b.graph_get(gr.g, pos.ctypes.data_as(fp), times.ctypes.data_as(fp), M.ctypes.data_as(fp)) == -3
+    assert (pos == SENT).all() and (times == SENT).all() and (M == SENT).all()
+    counts = (closure.SfcCounts * 1)()
+    C.memset(counts, 0xAB, C.sizeof(counts))
+    before = bytes(counts)
+    recs = np.full(2 * closure.RECORD.itemsize // 4, SENT, np.int32)  # room for two records
+    maps, views = (C.c_void_p * 1)(m.m.value), (closure.SfvView * 1)(v)
+    assert bld.b.build(bld.c, 1, maps, maps, views, views, (closure.SfcParams * 1)(closure.Params(stride=4)), recs.ctypes.data, 2, counts) == -3
+    assert bytes(counts) == before and (recs == SENT).all()
+
+
+def test_the_five_kinds_of_part_outlive_their_handle_or_go_before_it(hip_auto, golden):
+    """One 30 x 40 handle with two streams and one part of every kind, each used once. The handle goes first: every part is a
+    shell that refuses with SF_ERR_STATE, writes nothing and closes, twice. The parts go first, in the order they were made:
+    nothing errors. And a third handle gives what the first one gave."""
+    g = golden
+    s = small(hip_auto, g, 2)
+    parts = five_parts(s)
+    first = use_each_once(s, g, parts)
+    v = view.default_view(s, parts[0])
+    s.close()
+    refused_with_sentinels(s, parts, v)
+    for p in parts:
+        p.close()
+        p.close()
+    assert not parts[0].m and not parts[1].db and not parts[2].t and not parts[3].g and not parts[4].c
+    s = small(hip_auto, g, 2)
+    parts = five_parts(s)
+    use_each_once(s, g, parts)
+    for p in parts:
+        p.close()
+        p.close()
+    s.close()
+    s = small(hip_auto, g, 2)
+    parts = five_parts(s)
+    third = use_each_once(s, g, parts)
+    assert len(first) == len(third) == 10
+    for q, (x, y) in enumerate(zip(first, third)):
+        assert x.dtype == y.dtype and (np.array_equal(x, y, equal_nan=True) if x.dtype.kind == "f" else np.array_equal(x, y)), q
+    for p in parts:
+        p.close()
+    s.close()

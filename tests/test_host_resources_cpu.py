@@ -1,9 +1,11 @@
-"""The owner of the host side's device blocks, pinned blocks, events and streams (staticfusion_amd/csrc/sf_resources.h) and the
-per-call block of the companion interfaces (sf_call_block.h), the checks that need no GPU: a stand-alone C++ program includes
-the real headers, defines the HIP functions they call itself (malloc-backed, a set of live pointers, a log of calls, "fail the
-k-th acquiring call") and plays groups, growth, both rings, the layout rule, a call block reused at three sizes with its two
-cleared ranges, a call-local owner and the release through under the address and undefined-behaviour sanitizers -- once clean,
-then once for every acquiring call failing (a child process: nothing is loaded into python)."""
+"""The owner of the host side's device blocks, pinned blocks, events and streams (staticfusion_amd/csrc/sf_resources.h), the
+per-call block of the companion interfaces (sf_call_block.h) and the lifetime of what is created from a handle (sf_parts.h),
+the checks that need no GPU: a stand-alone C++ program includes the real headers, defines the HIP functions they call itself
+(malloc-backed, a set of live pointers, a log of calls, "fail the k-th acquiring call") and plays groups, growth, both rings,
+the layout rule, a call block reused at three sizes with its two cleared ranges, a call-local owner, the release, and the parts
+of two handles -- the handle first, the part first, a part never entered, a rebind, the shells destroyed -- through under the
+address and undefined-behaviour sanitizers -- once clean, then once for every acquiring call failing (a child process: nothing
+is loaded into python)."""
 import os
 import re
 import subprocess
@@ -22,7 +24,7 @@ def test_owner_growth_and_rings_under_sanitizers(tmp_path):
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert r.returncode == 0, (r.stdout.decode(), r.stderr.decode())
     m = re.match(r"ok (\d+)\n", r.stdout.decode())
-    assert m and int(m.group(1)) > 50 and not r.stderr  # the clean run and one run per acquiring call of it
+    assert m and int(m.group(1)) > 80 and not r.stderr  # the clean run and one run per acquiring call of it (61 before the parts)
 
 
 def test_the_host_sources_acquire_and_release_in_one_place():
@@ -65,3 +67,31 @@ def test_the_companion_host_sources_state_layout_block_and_refusals_once():
     assert len(re.findall(r"\bSfCallBlock\s+\w+;", body)) == 7
     # the header is host only and includes nothing of the product but sf_resources.h
     assert re.findall(r'#include\s+"([^"]+)"', read("sf_call_block.h")) == ["sf_resources.h"]
+
+
+def test_the_host_sources_state_the_lifetime_of_a_handles_parts_once():
+    """what is created from a handle (maps, keyframe databases, trackers, deformation graphs, closure builders) is entered in
+    one list of the handle and orphaned, destroyed and refused by one piece of code each (sf_parts.h, sf_host.h)"""
+    csrc = os.path.join(ROOT, "staticfusion_amd", "csrc")
+    read = lambda name: open(os.path.join(csrc, name)).read()
+    sources = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h", ".cpp"))]
+    for name in sources:
+        if name.endswith(".hip"):  # no part has an orphan function of its own
+            assert not re.search(r"^[\w\s*&:<>]*\borphan_\w*\s*\([^;{]*\)\s*(const\s*)?\{", read(name), re.M), name
+    host = read("sf_host.h")
+    body = host[host.index("struct sf_handle {"):host.index("// the surfel map")]
+    members = re.findall(r"(\w+)\s*(?:=[^;,]*|\{\}|\[[^\]]*\])*\s*[;,]", re.sub(r"//.*", "", body))
+    assert re.findall(r"\bSfParts\s+(\w+);", body) == ["parts"] and "parts" in members
+    assert not [m for m in members if m in ("maps", "keyframe_dbs", "trackers", "graphs", "builders")], members
+    assert not re.search(r"std::vector<\s*(struct\s+)?(sf_map|sfk_db|sft_tracker|sfd_graph|sfc_builder)\s*\*", body)
+    # the two refusals of a part and the refusal of a handle that is gone are made in check_part and check_live_handle alone
+    text = "has been destroyed"
+    for fn, count in (("check_part", 1), ("check_live_handle", 1)):
+        m = re.search(r"static inline int %s\(.*?\n}\n" % fn, host, re.S)
+        assert m and m.group(0).count(text) == count, fn
+        host = host.replace(m.group(0), "")
+    for name in sources:
+        assert text not in (host if name == "sf_host.h" else read(name)), name
+    # the header is host only and includes nothing of the product but sf_call_block.h / sf_resources.h
+    assert set(re.findall(r'#include\s+"([^"]+)"', read("sf_parts.h"))) <= {"sf_call_block.h", "sf_resources.h"}
+    assert not re.search(r"__global__|__device__|hip_runtime\.h", read("sf_parts.h"))
