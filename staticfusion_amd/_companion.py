@@ -1,5 +1,5 @@
 """What the bindings of the companion interfaces share (streams.py ``sfm_*``, map_window.py ``sfw_*``, view.py ``sfv_*``,
-score.py ``sfs_*``, keyframes.py ``sfk_*``, regions.py ``sfr_*``, align.py ``sfa_*``, join.py ``sfj_*``, tracks.py ``sft_*``, bodies.py ``sfb_*``, body_maps.py ``sfp_*``, deform.py ``sfd_*``, closure.py ``sfc_*``, carve.py ``sfe_*``). Their symbols are not part of the ABI of include/sf.h -- the CPU oracle does not have them -- so each
+score.py ``sfs_*``, keyframes.py ``sfk_*``, regions.py ``sfr_*``, align.py ``sfa_*``, join.py ``sfj_*``, tracks.py ``sft_*``, bodies.py ``sfb_*``, body_maps.py ``sfp_*``, deform.py ``sfd_*``, closure.py ``sfc_*``, carve.py ``sfe_*``, register.py ``sfg_*``). Their symbols are not part of the ABI of include/sf.h -- the CPU oracle does not have them -- so each
 has a table of its own, bound to the HIP library of an `Api` (the very ``ctypes.CDLL`` object: one copy of the library,
 one `sf_last_error`). Nothing here computes anything.
 """
@@ -52,7 +52,7 @@ def binder(prefix, subject, signatures, version, sizes=()):
 
 
 class HandleChild:
-    """base of the wrappers over what a binding creates from a solver's handle (sfk_db, sft_tracker, sfd_graph, sfc_builder, sfe_carver):
+    """base of the wrappers over what a binding creates from a solver's handle (sfk_db, sft_tracker, sfd_graph, sfc_builder, sfe_carver, sfg_registrar):
     `.solver`, `.api`, the binding `.b`, the pointer under the attribute `_ptr` names, `close()` -- the destroy function
     `_destroy` names, once, then a null pointer -- and a `__del__` that swallows"""
 

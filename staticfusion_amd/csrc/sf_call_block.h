@@ -1,10 +1,10 @@
-// sf_call_block.h — what one call of a companion interface (sfv_*, sfs_*, sfk_*, sfr_*, sfa_*, sfj_*, sft_*, sfb_*, sfp_*, sfd_*, sfc_*, sfe_*)
+// sf_call_block.h — what one call of a companion interface (sfv_*, sfs_*, sfk_*, sfr_*, sfa_*, sfj_*, sft_*, sfb_*, sfp_*, sfd_*, sfc_*, sfe_*, sfg_*)
 // lays out, fills and sends to the device: one rule for where the pieces of a call lie in a block (SfPlan), one type for
 // the block with the host copies its tables are filled from (SfCallBlock). Host only, no kernel, and nothing of the product
 // beyond sf_resources.h (tests/cpp/resources_host.cpp compiles it with g++ against HIP functions of its own).
 //
 // THE LIFETIME RULES, stated here for every part:
-//   - A block belongs to one part (a member of sf_handle, of a keyframe database, of a tracker, of a deformation graph, of a closure builder, of a carver). A call grows, fills and
+//   - A block belongs to one part (a member of sf_handle, of a keyframe database, of a tracker, of a deformation graph, of a closure builder, of a carver, of a registrar). A call grows, fills and
 //     reads its own part's block and leaves every other part's block alone, so the results a caller still holds from
 //     another part (sfv_last_large_sprites, a device-form output) stay what they were.
 //   - The block holds the host copies of the tables: a member outlives the asynchronous upload queued from it, which a local

@@ -6,7 +6,7 @@
 //   sf_call_block.h    the per-call block of a companion interface: its layout rule (SfPlan), the block with the host copies
 //                      of its tables (SfCallBlock) and the rules of their lifetime; host only, no kernel
 //   sf_parts.h         what is created from a handle and may outlive it (maps, keyframe databases, trackers, deformation
-//                      graphs, closure builders, carvers): their base (SfPart), the handle's list of them (SfParts) and the rules of
+//                      graphs, closure builders, carvers, registrars): their base (SfPart), the handle's list of them (SfParts) and the rules of
 //                      their lifetime; host only, no kernel
 //   sf_hip.hip         handle lifetime and the list of live handles, parameters, the builds of the frame kernel, launch()
 //   sf_hip_solver.hip  images in, frames (one or several per launch), results and debug planes out, measurement support
@@ -42,6 +42,8 @@
 //                      interface is include/sf_closure.h, symbols sfc_*)
 //   sf_hip_carve.hip   carving: surfels that later frames saw through leave their maps (sf_carve.h, sf_carve_rules.h; its
 //                      interface is include/sf_carve.h, symbols sfe_*)
+//   sf_hip_register.hip  registration: surfel maps aligned with each other on the voxel tables of their destinations
+//                      (sf_register.h, sf_register_rules.h; its interface is include/sf_register.h, symbols sfg_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,7 +77,7 @@ struct sf_handle {
     int *d_order = nullptr;   // KArgs::order storage (more streams than resident workgroups: a launch has a tail)
     int max_blocks_o5 = 0;  // throughput build: resident workgroups of the 5-per-CU kernel (0: not used)
     const FrameVariant *fv = nullptr;  // set by sf_create_ex
-    SfParts parts;  // what was created from this handle and lives: maps, keyframe databases, trackers, graphs, builders, carvers (sf_parts.h)
+    SfParts parts;  // what was created from this handle and lives: maps, keyframe databases, trackers, graphs, builders, carvers, registrars (sf_parts.h)
     bool reforder = false;  // the library's frame kernels are the reference-order build (sf_reforder.h)
     int cluster_grid = 0;  // SF_VARIANT_CLUSTER: blocks per launch (8 XCDs x streams per XCD x workgroups per stream)
     hipStream_t own_stream = nullptr;

@@ -1,5 +1,5 @@
 // sf_parts.h — the lifetime of everything that is created from an sf_handle and may outlive it: surfel maps (sf_map),
-// keyframe databases (sfk_db), region trackers (sft_tracker), deformation graphs (sfd_graph), closure builders (sfc_builder), carvers (sfe_carver).
+// keyframe databases (sfk_db), region trackers (sft_tracker), deformation graphs (sfd_graph), closure builders (sfc_builder), carvers (sfe_carver), registrars (sfg_registrar).
 // One base, SfPart, and one list in the handle, SfParts. Host only, no kernel, and nothing of the product beyond
 // sf_call_block.h / sf_resources.h (tests/cpp/resources_host.cpp compiles it with g++ against HIP functions of its own);
 // sf_handle is only named here. What needs the handle's members -- part_destroy, check_part -- is in sf_host.h.
