@@ -7,24 +7,16 @@
 //                         (M.x, M.y, M.z, drawn) and (n.x, n.y, n.z, 0). Every linearisation reads this image: a pair then
 //                         costs one 32-byte gather instead of the key (8 B), the surfel (48 B) and the ray (16 B).
 //   sfa_linearise_kernel  the hot path, once per iteration and once more at the end: flat over the column-major index of the
-//                         strided frame pixels along lanes, the 29 sums of sfa_system kept per lane in 64-bit integers
-//                         (products of 32-bit factors: v_mad_i64_i32), reduced across the wave with shuffles, across the
-//                         four waves through 928 bytes of LDS, and added to the entry's record with 64-bit integer atomics:
-//                         at most once per field per workgroup, and not at all for a field whose workgroup total is 0.
-//   sfa_step_kernel       one lane per entry between linearisations: FEW_PAIRS, the step of sf_align_step.h, the result.
-// An entry that has stopped or finished is marked in its AlignState; its workgroups of later launches read that word and
-// leave. There is no host synchronisation between the launches.
+//                         strided frame pixels along lanes, the 29 sums of the system (sf_p2p_system.h: quantise,
+//                         accumulate) kept per lane in 64-bit integers (products of 32-bit factors: v_mad_i64_i32) and
+//                         added to the entry's record by p2p_block_add (sf_p2p_device.h).
+//   sfa_step_kernel       one lane per entry between linearisations: p2p_step_entry (sf_p2p_device.h), then the result.
+// An entry that has stopped or finished is marked in its P2pState (uploaded with D = I and everything else 0); its workgroups
+// of later launches read that word and leave. There is no host synchronisation between the launches.
 #pragma once
 #include "../../include/sf_align.h"
-#include "sf_align_step.h"
+#include "sf_p2p_device.h"
 #include "sf_view_common.h"
-
-struct AlignState {  // per entry, uploaded with D = I and everything else 0
-    double D[12];
-    long long n_first, ss_first;
-    int done;        // 1: stopped or finished, the result is written
-    int iterations_done;
-};
 
 struct AlignArgs {
     const float *depth, *b;  // rows x cols column-major; b is read only with use_b
@@ -33,19 +25,12 @@ struct AlignArgs {
     float t0[16];            // view.pose
     vfloat4 *model;          // 2 x rows x cols: the model image
     long long *systems;      // (I + 1) records of 32 int64, zeroed before the first launch
-    AlignState *state;
+    P2pState *state;
     sfa_result *result;
 };
 
 #define SFA_NT 256
 #define SFA_PER_THREAD 4  // frame pixels per lane
-#define SFA_FIELDS 29
-
-__device__ __forceinline__ long long sfa_wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void sfa_model_kernel(const ViewArgs *vtab, const AlignArgs *atab) {
     const ViewArgs &a = vtab[blockIdx.y];
@@ -71,7 +56,6 @@ __global__ __launch_bounds__(256) void sfa_model_kernel(const ViewArgs *vtab, co
 }
 
 __global__ __launch_bounds__(SFA_NT) void sfa_linearise_kernel(const ViewArgs *vtab, const AlignArgs *atab, int it) {
-    __shared__ long long part[SFA_NT / 64][SFA_FIELDS];
     const ViewArgs &a = vtab[blockIdx.y];
     const AlignArgs &p = atab[blockIdx.y];
     if (it > p.iterations) return;  // an entry with fewer iterations than the call's largest
@@ -80,15 +64,13 @@ __global__ __launch_bounds__(SFA_NT) void sfa_linearise_kernel(const ViewArgs *v
     const int total = ny * nx;
     const int base = (int)blockIdx.x * (SFA_NT * SFA_PER_THREAD);
     if (base >= total) return;  // a workgroup of a larger entry of the batch
-    const AlignState &st = *p.state;
+    const P2pState &st = *p.state;
     if (st.done) return;
     float D[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) D[k] = (float)st.D[k];
     const int tid = threadIdx.x;
-    long long acc[SFA_FIELDS];
-#pragma unroll
-    for (int f = 0; f < SFA_FIELDS; f++) acc[f] = 0;
+    long long acc[p2p::FIELDS] = {};  // (not a zeroing loop: with one the compiler carries every sum through the pixel loop twice)
     const float gate = p.dist_max * p.dist_max;
 #pragma unroll 1
     for (int k = 0; k < SFA_PER_THREAD; k++) {
@@ -120,71 +102,31 @@ __global__ __launch_bounds__(SFA_NT) void sfa_linearise_kernel(const ViewArgs *v
         if (!(fabsf(r) <= p.dist_max)) continue;
         const PV3 c = pcross(Q, n);
         const float J[6] = {c.x, c.y, c.z, n.x, n.y, n.z};
-        int ai[6];
-#pragma unroll
-        for (int q = 0; q < 6; q++) ai[q] = (int)rintf(fminf(fmaxf(J[q], -64.f), 64.f) * 4096.f);  // |.| <= 2^18
-        const int rho = (int)rintf(r * 65536.f);                                                  // |.| <= 2^16
-        acc[0] += 1;
-        acc[1] += (long long)rho * rho;
-        int f = 8;
-#pragma unroll
-        for (int q = 0; q < 6; q++) {
-            acc[2 + q] += (long long)ai[q] * rho;
-#pragma unroll
-            for (int l = q; l < 6; l++) acc[f++] += (long long)ai[q] * ai[l];
-        }
+        int ai[6], rho;
+        p2p::quantise(J, r, ai, &rho);
+        p2p::accumulate(acc, ai, rho);
     }
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int f = 0; f < SFA_FIELDS; f++) {
-        const long long v = sfa_wave_sum(acc[f]);
-        if (lane == 0) part[wave][f] = v;
-    }
-    __syncthreads();
-    if (tid < SFA_FIELDS) {
-        long long v = 0;
-#pragma unroll
-        for (int q = 0; q < SFA_NT / 64; q++) v += part[q][tid];
-        if (v) __hip_atomic_fetch_add(as_global(p.systems) + (size_t)it * SFA_SYSTEM_WORDS + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    p2p_block_add<SFA_NT>(acc, as_global(p.systems) + (size_t)it * p2p::WORDS);
 }
 
+// (the I + 1 records of an entry are an output or scratch of their own: none is ever cleared, keep = 1)
 __global__ __launch_bounds__(64) void sfa_step_kernel(const AlignArgs *atab, int n_entries, int it) {
     const int q = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (q >= n_entries) return;
     const AlignArgs &p = atab[q];
-    AlignState &st = *p.state;
+    P2pState &st = *p.state;
     if (st.done) return;
-    const long long *w = p.systems + (size_t)it * SFA_SYSTEM_WORDS;
-    const long long n = w[0], ss = w[1];
-    if (it == 0) {
-        st.n_first = n;
-        st.ss_first = ss;
-    }
-    int status = SFA_OK;
-    if (it < p.iterations) {
-        if (n < (long long)p.min_pairs) {
-            status = SFA_FEW_PAIRS;
-        } else {
-            double Dn[12];
-            status = sfa_step_core((const int64_t *)w, p.damping, st.D, Dn);
-            if (status == SFA_STEP_OK) {
-#pragma unroll
-                for (int k = 0; k < 12; k++) st.D[k] = Dn[k];
-                st.iterations_done = it + 1;
-                return;  // on to the next linearisation
-            }
-        }
-    }
+    const P2pStop o = p2p_step_entry(st, p.systems + (size_t)it * p2p::WORDS, 1, p.iterations, p.min_pairs, p.damping, it);
+    if (!o.stopped) return;  // on to the next linearisation
     // the last linearisation of the entry, or a stop: the result, from the D the linearisation was taken at
     sfa_result r;
     sfa_compose_pose(p.t0, st.D, r.pose);
-    r.status = status;
+    r.status = o.status;
     r.iterations_done = st.iterations_done;
     r.n_first = st.n_first;
     r.ss_first = st.ss_first;
-    r.n_last = n;
-    r.ss_last = ss;
+    r.n_last = o.n;
+    r.ss_last = o.ss;
     r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
     *p.result = r;
     st.done = 1;

@@ -1,20 +1,17 @@
-// sf_align_step.h — the STEP of include/sf_align.h: from the 32 int64 words of a sfa_system and the estimate D, the damped
-// normal equations, their LDL^T solve without pivoting, the Cayley rotation of the solution and the updated estimate. fp64
+// sf_align_step.h — the STEP of include/sf_align.h: from the 32 int64 words of a system (sf_p2p_system.h) and the estimate D, the
+// damped normal equations, their LDL^T solve without pivoting, the Cayley rotation of the solution and the updated estimate. fp64
 // in the written order, only + - * / (no contraction: -ffp-contract=off), so the host (sfa_step of sf_hip_align.hip, and
-// tests/cpp/align_step_host.cpp under the sanitizers) and the device (sfa_step_kernel of sf_align.h) run the same text and
-// give the same bits. It includes nothing of the library and defines no kernel.
+// tests/cpp/align_step_host.cpp under the sanitizers) and the device (p2p_step_entry of sf_p2p_device.h) run the same text and
+// give the same bits. It includes nothing of the library but sf_p2p_system.h and defines no kernel.
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SFA_HD __host__ __device__
-#else
-#define SFA_HD
-#endif
+#include "sf_p2p_system.h"
 
-#define SFA_STEP_OK 0
-#define SFA_STEP_DEGENERATE 2
-#define SFA_SYSTEM_WORDS 32  // n, ss, g[6], H[21] (k <= l, row-wise), three reserved words
+#define SFA_HD P2P_HD
+#define SFA_STEP_OK p2p::OK
+#define SFA_STEP_DEGENERATE p2p::DEGENERATE
+#define SFA_SYSTEM_WORDS p2p::WORDS
 
 // w: the words of a sfa_system. Returns SFA_STEP_OK with D_out written (it may be D_in), or SFA_STEP_DEGENERATE with D_out
 // untouched.

@@ -16,27 +16,21 @@
 //                         64-bit global atomics, skipping zero words; a larger K takes the atomics on the global systems
 //                         directly. Both paths add the same integers. A workgroup whose tile holds no pixel of a region that
 //                         is still running leaves after reading its labels.
-//   sfb_step_kernel       one lane per (entry, region slot) between linearisations: FEW_PAIRS, the step of sf_align_step.h,
-//                         and on the last linearisation or a stop the result with W (sf_body_world.h).
+//   sfb_step_kernel       one lane per (entry, region slot) between linearisations: p2p_step_entry (sf_p2p_device.h), and on
+//                         the last linearisation or a stop the result with W (sf_body_world.h).
+// The system, its quantised row and its 29 sums: sf_p2p_system.h. The state of a region slot is a P2pState (sf_p2p_device.h).
 #pragma once
 #include "../../include/sf_bodies.h"
-#include "sf_align_step.h"
 #include "sf_body_world.h"
+#include "sf_p2p_device.h"
 #include "sf_surfel_geom.h"
 
 #define SFB_NT 256            // threads of the model and linearise kernels
 #define SFB_PB 2048           // frame-0 pixels per workgroup of the linearise kernel
 #define SFB_J (SFB_PB / SFB_NT)
-#define SFB_FIELDS 29         // the summed words of a system: n, ss, g[6], H[21]
+#define SFB_FIELDS p2p::FIELDS
 #define SFB_LDS_REGIONS 64    // the LDS budget of the workgroup table
 #define SFB_MAX_REGIONS 256
-
-struct BodyState {  // per (entry, region slot); set by sfb_model_kernel
-    double D[12];
-    long long n_first, ss_first;
-    int done;       // 1: stopped, finished, or a slot at or above K
-    int iterations_done;
-};
 
 struct BodyArgs {
     const float *z0;   // rows x cols column-major
@@ -52,12 +46,6 @@ struct BodyArgs {
     int iterations, min_pairs, K, pad;
 };
 
-__device__ __forceinline__ long long sfb_wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __device__ __forceinline__ PV3 sfb_back_project(float cx, float cy, float fx, float fy, int v, int u, float z) {
     const float du = (float)u - cx, dv = (float)v - cy;
     const float xu = du * z, yv = dv * z;
@@ -65,19 +53,11 @@ __device__ __forceinline__ PV3 sfb_back_project(float cx, float cy, float fx, fl
 }
 
 // ---- 1. target model ----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SFB_NT) void sfb_model_kernel(const BodyArgs *args, int rows, int cols, int M, BodyState *states) {
+__global__ __launch_bounds__(SFB_NT) void sfb_model_kernel(const BodyArgs *args, int rows, int cols, int M, P2pState *states) {
     const int q = blockIdx.y, tid = threadIdx.x;
     const BodyArgs &a = args[q];
     if (blockIdx.x == 0) {
-        for (int t = tid; t < M; t += SFB_NT) {
-            BodyState &s = states[(size_t)q * M + t];
-            for (int k = 0; k < 3; k++)
-                for (int c = 0; c < 4; c++) s.D[4 * k + c] = (double)a.D0[k + 4 * c];
-            s.n_first = 0;
-            s.ss_first = 0;
-            s.done = t >= a.K;
-            s.iterations_done = 0;
-        }
+        for (int t = tid; t < M; t += SFB_NT) p2p_state_init(states[(size_t)q * M + t], a.D0, t >= a.K);
     }
     if (a.K == 0) return;  // (no linearisation reads the model of an entry without regions)
     const int px = rows * cols;  // <= 2^24
@@ -115,12 +95,12 @@ __global__ __launch_bounds__(SFB_NT) void sfb_model_kernel(const BodyArgs *args,
 __device__ __forceinline__ void sfb_add_words(bool lds, long long *tab, long long *sys, int sys_slots, int c0, int lane, long long mine) {
     if (lane < SFB_FIELDS && mine) {
         if (lds) atomicAdd((unsigned long long *)&tab[(c0 - 1) * SFB_FIELDS + lane], (unsigned long long)mine);
-        else __hip_atomic_fetch_add(sys + (size_t)(c0 - 1) * sys_slots * SFA_SYSTEM_WORDS + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else __hip_atomic_fetch_add(sys + (size_t)(c0 - 1) * sys_slots * p2p::WORDS + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
 // systems: sys_slots records of 32 int64 per region slot; this launch adds to record `slot` of each
-__global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *args, int rows, int cols, int M, const BodyState *states, long long *systems,
+__global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *args, int rows, int cols, int M, const P2pState *states, long long *systems,
                                                                int sys_slots, int slot, int it) {
     __shared__ long long tab[SFB_LDS_REGIONS * SFB_FIELDS];
     __shared__ float Ds[SFB_MAX_REGIONS * 12];
@@ -131,7 +111,7 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
     if (it > a.iterations || K == 0) return;  // (the whole workgroup, like every return before the barriers below)
     const int px = rows * cols;
     const int base = (int)blockIdx.x * SFB_PB;
-    const BodyState *st = states + (size_t)q * M;
+    const P2pState *st = states + (size_t)q * M;
     for (int t = tid; t < K; t += SFB_NT) live[t] = !st[t].done;
     __syncthreads();
     bool any = false;
@@ -147,7 +127,7 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
     if (lds)
         for (int i = tid; i < K * SFB_FIELDS; i += SFB_NT) tab[i] = 0;
     __syncthreads();
-    long long *sys = systems + ((size_t)q * M * sys_slots + slot) * SFA_SYSTEM_WORDS;  // record `slot` of region slot 0 of the entry
+    long long *sys = systems + ((size_t)q * M * sys_slots + slot) * p2p::WORDS;  // record `slot` of region slot 0 of the entry
     const float gate = a.dist_max * a.dist_max;
     const float fcols = (float)cols, frows = (float)rows;
     int cur = 0;  // the region the lane's sums belong to, 0: none
@@ -187,9 +167,7 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
                                 if (pdot(d, d) <= gate && fabsf(r) <= a.dist_max) {
                                     const PV3 c = pcross(Q, n);
                                     const float Jv[6] = {c.x, c.y, c.z, n.x, n.y, n.z};
-#pragma unroll
-                                    for (int k = 0; k < 6; k++) ai[k] = (int)rintf(fminf(fmaxf(Jv[k], -64.f), 64.f) * 4096.f);  // |.| <= 2^18
-                                    rho = (int)rintf(r * 65536.f);                                                             // |.| <= 2^16
+                                    p2p::quantise(Jv, r, ai, &rho);
                                     t = l;
                                 }
                             }
@@ -211,7 +189,7 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
                 long long mine = 0;  // lane f ends with the total of word f
 #pragma unroll
                 for (int f = 0; f < SFB_FIELDS; f++) {
-                    const long long v = single ? __shfl(acc[f], leader, 64) : sfb_wave_sum(join ? acc[f] : 0ll);
+                    const long long v = single ? __shfl(acc[f], leader, 64) : wave_sum(join ? acc[f] : 0ll);
                     if (lane == f) mine = v;
                 }
                 sfb_add_words(lds, tab, sys, sys_slots, c0, lane, mine);
@@ -223,15 +201,7 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
         }
         if (t) {
             cur = t;
-            acc[0] += 1;
-            acc[1] += (long long)rho * rho;
-            int f = 8;
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-                acc[2 + k] += (long long)ai[k] * rho;
-#pragma unroll
-                for (int m = k; m < 6; m++) acc[f++] += (long long)ai[k] * ai[m];
-            }
+            p2p::accumulate(acc, ai, rho);
         }
     }
     if (lds) {
@@ -240,7 +210,7 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
             const long long v = tab[i];
             if (v) {
                 const int t0 = i / SFB_FIELDS;
-                __hip_atomic_fetch_add(sys + (size_t)t0 * sys_slots * SFA_SYSTEM_WORDS + (i - t0 * SFB_FIELDS), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(sys + (size_t)t0 * sys_slots * p2p::WORDS + (i - t0 * SFB_FIELDS), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -249,49 +219,27 @@ __global__ __launch_bounds__(SFB_NT) void sfb_linearise_kernel(const BodyArgs *a
 // ---- 3. step ------------------------------------------------------------------------------------------------------------
 // keep != 0: the systems are an output, record `it` of every region slot stays; else the one record of a slot is cleared
 // for the next linearisation once it has been read.
-__global__ __launch_bounds__(64) void sfb_step_kernel(const BodyArgs *args, int n_slots, int M, BodyState *states, long long *systems, int sys_slots, int slot,
+__global__ __launch_bounds__(64) void sfb_step_kernel(const BodyArgs *args, int n_slots, int M, P2pState *states, long long *systems, int sys_slots, int slot,
                                                       int keep, sfb_motion *motions, int it) {
     const int g = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (g >= n_slots) return;
     const int q = g / M, t = g - q * M;
     const BodyArgs &a = args[q];
     if (t >= a.K) return;
-    BodyState &st = states[g];
+    P2pState &st = states[g];
     if (st.done) return;
-    long long *rec = systems + ((size_t)g * sys_slots + slot) * SFA_SYSTEM_WORDS;
-    int64_t w[SFA_SYSTEM_WORDS];
-    for (int f = 0; f < SFA_SYSTEM_WORDS; f++) w[f] = f < SFB_FIELDS ? rec[f] : 0;
-    if (!keep)
-        for (int f = 0; f < SFB_FIELDS; f++) rec[f] = 0;
-    const long long n = w[0], ss = w[1];
-    if (it == 0) {
-        st.n_first = n;
-        st.ss_first = ss;
-    }
-    int status = SFB_OK;
-    if (it < a.iterations) {
-        if (n < (long long)a.min_pairs) {
-            status = SFB_FEW_PAIRS;
-        } else {
-            double Dn[12];
-            status = sfa_step_core(w, a.damping, st.D, Dn);
-            if (status == SFA_STEP_OK) {
-                for (int k = 0; k < 12; k++) st.D[k] = Dn[k];
-                st.iterations_done = it + 1;
-                return;  // on to the next linearisation
-            }
-        }
-    }
+    const P2pStop o = p2p_step_entry(st, systems + ((size_t)g * sys_slots + slot) * p2p::WORDS, keep, a.iterations, a.min_pairs, a.damping, it);
+    if (!o.stopped) return;  // on to the next linearisation
     // the last linearisation of the region, or a stop: the result, from the D the linearisation was taken at
     sfb_motion r;
     sfb_estimate_as_4x4(st.D, r.d);
     sfb_world_core(a.pose0, a.pose1, st.D, r.w);
-    r.status = status;
+    r.status = o.status;
     r.iterations_done = st.iterations_done;
     r.n_first = st.n_first;
     r.ss_first = st.ss_first;
-    r.n_last = n;
-    r.ss_last = ss;
+    r.n_last = o.n;
+    r.ss_last = o.ss;
     r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
     motions[g] = r;
     st.done = 1;

@@ -51,12 +51,6 @@ __device__ __forceinline__ bool sfc_winner(const ViewArgs &a, int x, int y, floa
     return true;
 }
 
-__device__ __forceinline__ long long sfc_wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(SFC_NT) void sfc_sample_kernel(const ViewArgs *vtab, const ClosureArgs *ctab) {
     __shared__ long long part[SFC_NT / 64][SFC_FIELDS];
@@ -95,8 +89,8 @@ __global__ __launch_bounds__(SFC_NT) void sfc_sample_kernel(const ViewArgs *vtab
         cnt[5] = __popcll(b_link);
         cnt[6] = __popcll(b_pin);
         cnt[7] = __popcll(__ballot((mask & SFC_BIT_LINK_DROPPED) != 0)) + __popcll(__ballot((mask & SFC_BIT_PIN_DROPPED) != 0));
-        q_dz = sfc_wave_sum(q_dz);
-        q_shift = sfc_wave_sum(q_shift);
+        q_dz = wave_sum(q_dz);
+        q_shift = wave_sum(q_shift);
         if (lane == 0) {
 #pragma unroll
             for (int f = 0; f < 8; f++) part[wave][f] = cnt[f];

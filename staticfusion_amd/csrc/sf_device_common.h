@@ -234,6 +234,18 @@ __device__ __forceinline__ float wave_max_f32(float v) {
     SF_DPP_REDUCE(b, dpp_i32, sf_op_maxi)
     return __int_as_float(__builtin_amdgcn_readlane(b, 63));
 }
+// The integer wave sums of the companion kernels (sf_p2p_device.h, sf_bodies.h, sf_score.h, sf_closure.h, sf_tracks.h,
+// sf_regions.h): a butterfly of shuffles, every lane gets the total. Integers: the order of the additions does not show.
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
 
 // Exclusive scan of block_counts[0 .. n_blocks) in place by ONE 1024-thread workgroup, 1024 counts per trip; thread 0 gets the
 // total. The scan stage of the ordered compactions (sf_fusion.h: clean; sf_map_window.h: partition).

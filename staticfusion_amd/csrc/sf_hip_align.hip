@@ -1,5 +1,6 @@
 // sf_hip_align.hip — libsf_hip.so, the interface of include/sf_align.h (symbols sfa_*): damped point-to-plane refinement of
-// many (map, candidate pose, frame) entries per call (kernels: sf_align.h; the step: sf_align_step.h). The maps are drawn by
+// many (map, candidate pose, frame) entries per call (kernels: sf_align.h; the system: sf_p2p_system.h; the step: sf_align_step.h;
+// the state of an entry and the step's bookkeeping: sf_p2p_device.h). The maps are drawn by
 // the drawing stage of the views (sfv_plan / sfv_draw_keys of sf_hip_view.hip) into the call block sf_handle::align
 // (sf_call_block.h: layout, growth and lifetime); behind the drawing layout lie the entry table with the entries' states, the
 // model images, the systems, the result records and -- for the host-pointer calls -- the uploaded frames. A refine call only
@@ -12,9 +13,9 @@
 #define SFA_VERSION 1
 static_assert(sizeof(sfa_params) == 32, "include/sf_align.h: sfa_params is 32 bytes");
 static_assert(sizeof(sfa_result) == 128, "include/sf_align.h: sfa_result is 128 bytes");
-static_assert(sizeof(sfa_system) == 256 && sizeof(sfa_system) == SFA_SYSTEM_WORDS * sizeof(long long) && SFA_FIELDS == 29,
-              "sfa_linearise_kernel adds the first 29 int64 fields of a sfa_system");
-static_assert(SFA_STEP_OK == SFA_OK && SFA_STEP_DEGENERATE == SFA_DEGENERATE, "sf_align_step.h restates the status codes");
+static_assert(sizeof(sfa_system) == p2p::WORDS * sizeof(long long) && offsetof(sfa_system, reserved) == p2p::FIELDS * sizeof(long long),
+              "include/sf_align.h: sfa_system is the system of sf_p2p_system.h, its summed words first");
+static_assert(SFA_OK == p2p::OK && SFA_FEW_PAIRS == p2p::FEW_PAIRS && SFA_DEGENERATE == p2p::DEGENERATE, "include/sf_align.h: the status codes of sf_p2p_system.h");
 
 static_assert(offsetof(sfa_params, damping) == 12, "the four floats of sfa_params are consecutive");
 static int check_params(const sfa_params *p) {
@@ -61,7 +62,7 @@ static int refine(const char *what, CallForm form, sf_handle *h, int n, sf_map *
     const size_t sys_bytes = (size_t)n * (size_t)(max_it + 1) * sizeof(sfa_system);
     ViewPlan p;
     sfv_plan(p, n, jobs.data(), views, 0);
-    const size_t tab_bytes = (size_t)n * (sizeof(AlignArgs) + sizeof(AlignState));  // the table, then the states: one upload
+    const size_t tab_bytes = (size_t)n * (sizeof(AlignArgs) + sizeof(P2pState));  // the table, then the states: one upload
     const size_t o_atab = p.take(tab_bytes);
     const size_t o_state = o_atab + (size_t)n * sizeof(AlignArgs);
     const size_t o_res = form == FORM_DEVICE ? 0 : p.take((size_t)n * sizeof(sfa_result));
@@ -83,7 +84,7 @@ static int refine(const char *what, CallForm form, sf_handle *h, int n, sf_map *
     unsigned char *base = h->align.dev;
     // ---- the entry table and the states (host copy 1, zeroed: a state starts from zeros; the view table is copy 0)
     AlignArgs *atab = (AlignArgs *)h->align.zeroed<unsigned char>(tab_bytes, 1);
-    AlignState *states = (AlignState *)(atab + n);
+    P2pState *states = (P2pState *)(atab + n);
     sfa_result *d_res = form == FORM_DEVICE ? (sfa_result *)results : (sfa_result *)(base + o_res);
     long long *d_sys = (form == FORM_DEVICE && systems_out) ? (long long *)systems_out : (long long *)(base + o_sys);
     for (int q = 0; q < n; q++) {
@@ -107,8 +108,8 @@ static int refine(const char *what, CallForm form, sf_handle *h, int n, sf_map *
         s.iterations = sp.iterations; s.stride = sp.stride; s.min_pairs = sp.min_pairs; s.use_b = sp.use_b;
         for (int k = 0; k < 16; k++) s.t0[k] = views[q].pose[k];
         s.model = (vfloat4 *)(base + o_model[(size_t)q]);
-        s.systems = d_sys + (size_t)q * (size_t)(max_it + 1) * SFA_SYSTEM_WORDS;
-        s.state = (AlignState *)(base + o_state) + q;
+        s.systems = d_sys + (size_t)q * (size_t)(max_it + 1) * p2p::WORDS;
+        s.state = (P2pState *)(base + o_state) + q;
         s.result = d_res + q;
         states[(size_t)q].D[0] = states[(size_t)q].D[5] = states[(size_t)q].D[10] = 1.0;  // D0 = I
     }

@@ -1,6 +1,6 @@
 // sf_hip_bodies.hip — libsf_hip.so, the interface of include/sf_bodies.h (symbols sfb_*): the rigid motion of every moving
-// region of a batch of frame pairs, by damped point-to-plane steps (kernels: sf_bodies.h; the step: sf_align_step.h; the world
-// motion: sf_body_world.h). Everything a call needs lies in the call block sf_handle::bodies (sf_call_block.h: layout, growth
+// region of a batch of frame pairs, by damped point-to-plane steps (kernels: sf_bodies.h; the system: sf_p2p_system.h; the step:
+// sf_align_step.h; the state of a region and the step's bookkeeping: sf_p2p_device.h; the world motion: sf_body_world.h). Everything a call needs lies in the call block sf_handle::bodies (sf_call_block.h: layout, growth
 // and lifetime): the entry table, the pair table, the region states, the model images, the systems and -- for the host form --
 // the uploaded frames and the results. A call only reads its inputs. The number of launches is fixed by the largest
 // `iterations` of the call; nothing is read back between them.
@@ -13,12 +13,11 @@ static_assert(sizeof(sfb_params) == 32, "include/sf_bodies.h: sfb_params is 32 b
 static_assert(sizeof(sfb_motion) == 192, "include/sf_bodies.h: sfb_motion is 192 bytes");
 static_assert(sizeof(sfb_camera) == sizeof(sft_camera) && offsetof(sfb_camera, cx) == offsetof(sft_camera, cx) && offsetof(sfb_camera, fy) == offsetof(sft_camera, fy),
               "include/sf_bodies.h: sfb_camera is the camera of include/sf_tracks.h");
-static_assert(sizeof(sfb_system) == sizeof(sfa_system) && offsetof(sfb_system, g) == offsetof(sfa_system, g) && offsetof(sfb_system, H) == offsetof(sfa_system, H) &&
-                  sizeof(sfb_system) == SFA_SYSTEM_WORDS * sizeof(long long),
-              "include/sf_bodies.h: sfb_system is the system record of include/sf_align.h");
-static_assert(SFB_OK == SFA_OK && SFB_FEW_PAIRS == SFA_FEW_PAIRS && SFB_DEGENERATE == SFA_DEGENERATE && SFA_STEP_DEGENERATE == SFB_DEGENERATE,
-              "include/sf_bodies.h restates the status codes of include/sf_align.h");
-static_assert(sizeof(BodyState) == 120 && SFB_PB % SFB_NT == 0 && SFB_FIELDS <= 64, "sf_bodies.h: one lane per summed word");
+static_assert(sizeof(sfb_system) == p2p::WORDS * sizeof(long long) && offsetof(sfb_system, g) == 16 && offsetof(sfb_system, H) == 64 &&
+                  offsetof(sfb_system, reserved) == p2p::FIELDS * sizeof(long long),
+              "include/sf_bodies.h: sfb_system is the system of sf_p2p_system.h, its summed words first");
+static_assert(SFB_OK == p2p::OK && SFB_FEW_PAIRS == p2p::FEW_PAIRS && SFB_DEGENERATE == p2p::DEGENERATE, "include/sf_bodies.h: the status codes of sf_p2p_system.h");
+static_assert(SFB_PB % SFB_NT == 0 && SFB_FIELDS <= 64, "sf_bodies.h: one lane per summed word");
 
 static_assert(offsetof(sfb_params, damping) == 12, "the four floats of sfb_params are consecutive");
 static int check_params(const sfb_params *p) {
@@ -72,7 +71,7 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
     SfPlan p;
     const size_t o_args = p.take((size_t)n * sizeof(BodyArgs));
     const size_t o_pairs = pairs ? p.take(slots_total * 4) : 0;
-    const size_t o_state = p.take(slots_total * sizeof(BodyState));
+    const size_t o_state = p.take(slots_total * sizeof(P2pState));
     const size_t o_sys = (device_form && systems_out) ? 0 : p.take(sys_bytes);
     const size_t o_mot = device_form ? 0 : p.take(slots_total * sizeof(sfb_motion));
     const size_t o_model = p.take((size_t)n * px * 2 * sizeof(vfloat4));
@@ -114,7 +113,7 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
         a.iterations = sp.iterations; a.min_pairs = sp.min_pairs; a.K = n_regions[q];
     }
     const BodyArgs *d_args = (const BodyArgs *)(base + o_args);
-    BodyState *d_state = (BodyState *)(base + o_state);
+    P2pState *d_state = (P2pState *)(base + o_state);
     long long *d_sys = (device_form && systems_out) ? (long long *)systems_out : (long long *)(base + o_sys);
     sfb_motion *d_mot = device_form ? (sfb_motion *)motions : (sfb_motion *)(base + o_mot);
     if (int e = h->bodies.upload(o_args, tab, (size_t)n * sizeof(BodyArgs), h->stream)) return e;
@@ -132,7 +131,7 @@ static int estimate(const char *what, bool device_form, sf_handle *h, int rows, 
     for (int it = 0; it <= max_it; it++) {
         const int slot = keep ? it : 0;
         hipLaunchKernelGGL(sfb_linearise_kernel, dim3((unsigned)((px + SFB_PB - 1) / SFB_PB), un), dim3(SFB_NT), 0, h->stream, d_args, rows, cols, M,
-                           (const BodyState *)d_state, d_sys, sys_slots, slot, it);
+                           (const P2pState *)d_state, d_sys, sys_slots, slot, it);
         hipLaunchKernelGGL(sfb_step_kernel, dim3((unsigned)((slots_total + 63) / 64)), dim3(64), 0, h->stream, d_args, (int)slots_total, M, d_state, d_sys, sys_slots,
                            slot, keep, d_mot, it);
     }

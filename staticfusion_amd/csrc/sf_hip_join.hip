@@ -1,5 +1,5 @@
 // sf_hip_join.hip — libsf_hip.so, the interface of include/sf_join.h (symbols sfj_*): maps thinned to one surfel per voxel and
-// maps merged without storing a surface twice, many per call (kernels: sf_join.h; key, rank and hash: sf_join_key.h). The
+// maps merged without storing a surface twice, many per call (kernels: sf_voxel_table.h, sf_join.h; key, rank and hash: sf_join_key.h). The
 // voxel tables, the remembered slots, the ballots, the block counts, the counters and the two entry tables of a call lie in
 // the call block sf_handle::join (sf_call_block.h: layout, growth and lifetime). A thin partitions a map into its idle second
 // buffer like a cull, with the scan and the ordered write of the bounded maps (sfw_launch_scan / sfw_launch_write); a merge

@@ -1,6 +1,7 @@
 // sf_hip_register.hip — libsf_hip.so, the interface of include/sf_register.h (symbols sfg_*): surfel maps registered against each
 // other on the voxel tables of their destinations, many (destination, source, start) entries per call (kernels: sf_register.h;
-// the rules host and device share: sf_register_rules.h; the table and its insert kernel: sf_join.h; the step: sf_align_step.h).
+// the rules host and device share: sf_register_rules.h; the table and its insert kernel: sf_voxel_table.h; the system:
+// sf_p2p_system.h; the step: sf_align_step.h; the state of an entry and the step's bookkeeping: sf_p2p_device.h).
 // A registrar owns one call block (sf_call_block.h) under an owner of its own, as a carver does. In it lie, in one piece and
 // one upload, the JoinArgs of the distinct tables and the entry table; then what is cleared to 0 (the tables' counters and bids,
 // the entries' counters, results and systems), what is cleared to ~0 (the keys), and the rest (the slots the insert remembers, the
@@ -15,9 +16,10 @@
 
 #define SFG_VERSION 1
 static_assert(sizeof(sfg_params) == 32, "include/sf_register.h: sfg_params is 32 bytes");
-static_assert(sizeof(sfg_system) == 256 && sizeof(sfg_system) == SFG_SYSTEM_WORDS * sizeof(int64_t), "include/sf_register.h: sfg_system is 32 int64 words");
+static_assert(sizeof(sfg_system) == p2p::WORDS * sizeof(int64_t) && offsetof(sfg_system, reserved) == p2p::FIELDS * sizeof(int64_t),
+              "include/sf_register.h: sfg_system is the system of sf_p2p_system.h, its summed words first");
 static_assert(sizeof(sfg_result) == 128, "include/sf_register.h: sfg_result is 128 bytes");
-static_assert(SFG_SYSTEM_WORDS == SFA_SYSTEM_WORDS && SFG_OK == SFA_STEP_OK && SFG_DEGENERATE == SFA_STEP_DEGENERATE, "the step of sf_align_step.h applies unchanged");
+static_assert(SFG_OK == p2p::OK && SFG_FEW_PAIRS == p2p::FEW_PAIRS && SFG_DEGENERATE == p2p::DEGENERATE, "include/sf_register.h: the status codes of sf_p2p_system.h");
 static_assert(sizeof(RegArgs) % 8 == 0 && sizeof(JoinArgs) % 8 == 0, "the two tables follow one another aligned");
 
 struct SF_INTERNAL sfg_registrar : SfPart {
@@ -163,7 +165,7 @@ int sfg_register_maps(sfg_registrar *reg, int n, sf_map *const *dst, sf_map *con
     for (int t = 0; t < nt; t++) o_keys[(size_t)t] = p.take((size_t)slots[(size_t)t] * 8);
     p.rest_from_here();
     for (int t = 0; t < nt; t++) o_slot[(size_t)t] = p.take((size_t)dst[first_entry[(size_t)t]]->count * sizeof(int));
-    const size_t o_state = p.take((size_t)n * sizeof(RegState));
+    const size_t o_state = p.take((size_t)n * sizeof(P2pState));
     std::vector<int> total((size_t)n);
     for (int q = 0; q < n; q++) {
         total[(size_t)q] = (int)strided(src[q]->count, params[q].stride);
@@ -203,7 +205,7 @@ int sfg_register_maps(sfg_registrar *reg, int n, sf_map *const *dst, sf_map *con
         a.min_pairs = params[q].min_pairs;
         for (int k = 0; k < 16; k++) a.T0[k] = T0 ? T0[(size_t)q * 16 + k] : (k % 5 == 0 ? 1.f : 0.f);
         a.systems = (long long *)(base + o_sys) + (size_t)q * sys_slots * SFG_SYSTEM_WORDS;
-        a.state = (RegState *)(base + o_state) + q;
+        a.state = (P2pState *)(base + o_state) + q;
         a.result = (sfg_result *)(base + o_back) + q;
         a.counts = (int *)(base + o_back + res_bytes) + (size_t)q * SFG_COUNT_WORDS;
         a.pairs = (pairs_out && pairs_out[q]) ? (int *)(base + o_pairs[(size_t)q]) : nullptr;

@@ -27,9 +27,12 @@
 //   sf_hip_regions.hip moving regions: connected components of the dynamic pixels, numbered, with statistics
 //                      (sf_regions.h; its interface is include/sf_regions.h, symbols sfr_*)
 //   sf_hip_align.hip   poses refined against maps: damped point-to-plane steps with integer normal equations
-//                      (sf_align.h, sf_align_step.h; its interface is include/sf_align.h, symbols sfa_*)
+//                      (sf_align.h; its interface is include/sf_align.h, symbols sfa_*). What it shares with the region
+//                      motion and the registration: the quantised system (sf_p2p_system.h), the step (sf_align_step.h), and
+//                      an entry's state, the workgroup's reduction and the step's bookkeeping (sf_p2p_device.h)
 //   sf_hip_join.hip    maps joined and thinned on a voxel grid: merge, decimate (sf_join.h, sf_join_key.h; its interface
-//                      is include/sf_join.h, symbols sfj_*)
+//                      is include/sf_join.h, symbols sfj_*). The voxel table and its insert kernel, which the registration
+//                      uses too: sf_voxel_table.h
 //   sf_hip_tracks.hip  region tracks: the moving regions followed from frame to frame, with a metric box (sf_tracks.h,
 //                      sf_track_assign.h; its interface is include/sf_tracks.h, symbols sft_*)
 //   sf_hip_bodies.hip  region motion: the rigid motion of every moving region between two frames (sf_bodies.h,
@@ -43,7 +46,7 @@
 //   sf_hip_carve.hip   carving: surfels that later frames saw through leave their maps (sf_carve.h, sf_carve_rules.h; its
 //                      interface is include/sf_carve.h, symbols sfe_*)
 //   sf_hip_register.hip  registration: surfel maps aligned with each other on the voxel tables of their destinations
-//                      (sf_register.h, sf_register_rules.h; its interface is include/sf_register.h, symbols sfg_*)
+//                      (sf_register.h, sf_register_rules.h, sf_voxel_table.h; its interface is include/sf_register.h, symbols sfg_*)
 #pragma once
 #include <hip/hip_runtime.h>
 

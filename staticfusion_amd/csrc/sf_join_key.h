@@ -1,8 +1,8 @@
 // sf_join_key.h — the definitions of include/sf_join.h that the host and the device share: the voxel key of a position, the
 // rank of a confidence, the size of a table, the first slot of a key and the transform of a merge. Plain C++, fp32 in the
 // written order, one operation per expression (no contraction: -ffp-contract=off), so the host (sfj_voxel_key, sfj_hash_slot and
-// sfj_table_slots of sf_hip_join.hip, and tests/cpp/join_key_host.cpp under the sanitizers) and the device (sf_join.h) run the
-// same text and give the same bits. It includes nothing of the library and defines no kernel.
+// sfj_table_slots of sf_hip_join.hip, and tests/cpp/join_key_host.cpp under the sanitizers) and the device (sf_voxel_table.h, sf_join.h) run
+// the same text and give the same bits. It includes nothing of the library and defines no kernel.
 #pragma once
 #include <math.h>
 #include <stdint.h>

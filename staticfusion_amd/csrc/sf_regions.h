@@ -224,12 +224,6 @@ __global__ __launch_bounds__(SFR_NT) void sfr_flatten_kernel(RgGeom g, int *prov
 }
 
 // ---- numbering ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int rg_wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(SFR_NT) void sfr_count_kernel(const RgArgs *args, RgGeom g, const int *prov, const int *cnt, int *block_counts,
                                                            sfr_summary *summaries) {
     __shared__ int part[3][SFR_NT / 64];
@@ -249,9 +243,9 @@ __global__ __launch_bounds__(SFR_NT) void sfr_count_kernel(const RgArgs *args, R
             }
         }
     }
-    n_mask = rg_wave_sum(n_mask);
-    n_comp = rg_wave_sum(n_comp);
-    n_reg = rg_wave_sum(n_reg);
+    n_mask = wave_sum(n_mask);
+    n_comp = wave_sum(n_comp);
+    n_reg = wave_sum(n_reg);
     if ((tid & 63) == 0) {
         part[0][tid >> 6] = n_mask;
         part[1][tid >> 6] = n_comp;
@@ -367,12 +361,6 @@ __device__ __forceinline__ int rg_wave_max(int v) {
     for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
     return v;
 }
-__device__ __forceinline__ long long rg_wave_sum64(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // Every lane stays to the end (lanes past the image hold nothing): the wave adds what its lanes hold for one region -- the
 // region of its first lane that holds any -- with shuffles and one lane writes it; lanes that end in another region write
 // their own. The sums are integers, so who adds what changes nothing.
@@ -441,9 +429,9 @@ __global__ __launch_bounds__(SFR_NT) void sfr_final_kernel(const RgArgs *args, R
     w.u_max = rg_wave_max(join ? acc.u_max : -1);
     w.z_min = rg_wave_min(join ? acc.z_min : 0x7fffffff);
     w.z_max = rg_wave_max(join ? acc.z_max : -1);
-    w.sum_v = rg_wave_sum64(join ? acc.sum_v : 0);
-    w.sum_u = rg_wave_sum64(join ? acc.sum_u : 0);
-    w.sum_z = rg_wave_sum64(join ? acc.sum_z : 0);
-    w.sum_b = rg_wave_sum64(join ? acc.sum_b : 0);
+    w.sum_v = wave_sum(join ? acc.sum_v : 0);
+    w.sum_u = wave_sum(join ? acc.sum_u : 0);
+    w.sum_z = wave_sum(join ? acc.sum_z : 0);
+    w.sum_b = wave_sum(join ? acc.sum_b : 0);
     if (((int)threadIdx.x & 63) == leader) w.flush(rec, max_regions);
 }

@@ -1,22 +1,23 @@
 // sf_register_rules.h — the rules SAMPLE, PAIR and the row of include/sf_register.h that the host and the device share: whether a
 // source surfel is sampled, where the estimate puts it, which representative of the destination's voxel table is its partner, the
-// gates, and the quantised point-to-plane row with its 29 sums. Plain C++, fp32 in the written order, one operation per expression
-// (no contraction: -ffp-contract=off), so the host (sfg_linearise of sf_hip_register.hip, and tests/cpp/register_rules_host.cpp
-// under the sanitizers) and the device (sf_register.h) run the same text and give the same bits. It includes nothing of the
-// library beyond sf_join_key.h (the key, the rank, the hash) and defines no kernel. The table is a template parameter only so
-// that the device can hand in pointers to global memory and load 16 bytes at a time; a table offers
+// gates, and the point-to-plane row, quantised and summed by sf_p2p_system.h. Plain C++, fp32 in the written order, one operation
+// per expression (no contraction: -ffp-contract=off), so the host (sfg_linearise of sf_hip_register.hip, and
+// tests/cpp/register_rules_host.cpp under the sanitizers) and the device (sf_register.h) run the same text and give the same bits.
+// It includes nothing of the library beyond sf_join_key.h (the key, the rank, the hash) and sf_p2p_system.h, and defines no
+// kernel. The table is a template parameter only so that the device can hand in pointers to global memory and load 16 bytes at a
+// time; a table offers
 //   slots, log2_slots, count      the size of the table and the number of surfels that filled it
-//   key(slot), best(slot)         the two words of a slot (sf_join.h: the key or SFJ_EMPTY; the highest bid of the voxel)
+//   key(slot), best(slot)         the two words of a slot (sf_voxel_table.h: the key or SFJ_EMPTY; the highest bid of the voxel)
 //   quad(r, which)                floats 4 * which .. 4 * which + 3 of destination surfel r
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "sf_join_key.h"
+#include "sf_p2p_system.h"
 
 #define SFG_HD SFJ_HD
-#define SFG_FIELDS 29          // the summed words of a system: n, ss, g[6], H[21]
-#define SFG_SYSTEM_WORDS 32    // ... and three reserved words written as 0
+#define SFG_SYSTEM_WORDS p2p::WORDS
 #define SFG_NOT_PAIRED (-1)
 #define SFG_NOT_SAMPLED (-2)
 #define SFG_MAX_SAMPLED (1 << 24)
@@ -165,25 +166,9 @@ SFG_HD static inline SfgPair sfg_pair_core(const Table &t, const SfgRule &r, con
     const float zx = Qz * nx, xz = nz * Qx;
     const float xy = Qx * ny, yx = nx * Qy;
     const float J[6] = {yz - zy, zx - xz, xy - yx, nx, ny, nz};
-    for (int k = 0; k < 6; k++) {
-        const float lo = fmaxf(J[k], -64.0f);
-        const float cl = fminf(lo, 64.0f);
-        o.a[k] = (int)rintf(cl * 4096.0f);
-    }
-    o.rho = (int)rintf(res * 65536.0f);
+    p2p::quantise(J, res, o.a, &o.rho);
     o.partner = partner;
     return o;
-}
-
-// the 29 sums take one pair
-SFG_HD static inline void sfg_accumulate(long long *acc, const SfgPair &o) {
-    acc[0] += 1;
-    acc[1] += (long long)o.rho * o.rho;
-    int f = 8;
-    for (int k = 0; k < 6; k++) {
-        acc[2 + k] += (long long)o.a[k] * o.rho;
-        for (int l = k; l < 6; l++) acc[f++] += (long long)o.a[k] * o.a[l];
-    }
 }
 
 // ---- the host's table: the same slots, filled one surfel after the other
@@ -245,7 +230,7 @@ static inline bool sfg_linearise_host(const Table &t, const SfgRule &r, const fl
         const SfgPair o = sfg_pair_core(t, r, E, SfgF4{s[0], s[1], s[2], s[3]}, SfgF4{s[8], s[9], s[10], s[11]});
         lost = lost || o.lost;
         if (o.outside) outside++;
-        if (o.partner >= 0) sfg_accumulate(words, o);
+        if (o.partner >= 0) p2p::accumulate(words, o.a, o.rho);
         if (pairs) pairs[e] = o.partner;
     }
     *n_sampled = sampled;

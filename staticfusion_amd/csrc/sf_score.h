@@ -25,12 +25,6 @@ struct ScoreArgs {
 #define SFS_PER_THREAD 4  // pixels per lane: a workgroup covers 1024 consecutive pixels, a QVGA view sends 75 x 10 atomics
 #define SFS_FIELDS 10
 
-__device__ __forceinline__ long long sfs_wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(SFS_NT) void sfs_score_kernel(const ViewArgs *vtab, const ScoreArgs *stab) {
     __shared__ long long part[SFS_NT / 64][SFS_FIELDS];
     const ViewArgs &a = vtab[blockIdx.y];
@@ -97,9 +91,9 @@ __global__ __launch_bounds__(SFS_NT) void sfs_score_kernel(const ViewArgs *vtab,
             p.cls[idx] = code;
         }
     }
-    s_abs = sfs_wave_sum(s_abs);
-    s_sq = sfs_wave_sum(s_sq);
-    s_grey = sfs_wave_sum(s_grey);
+    s_abs = wave_sum(s_abs);
+    s_sq = wave_sum(s_sq);
+    s_grey = wave_sum(s_grey);
     const int wave = tid >> 6, lane = tid & 63;
     if (lane == 0) {
 #pragma unroll

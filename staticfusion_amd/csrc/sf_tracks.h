@@ -47,11 +47,6 @@ struct TkArgs {
     int has_prev, min_overlap, min_share, use_gate;
 };
 
-__device__ __forceinline__ int tk_wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 __device__ __forceinline__ int tk_wave_min(int v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
@@ -62,12 +57,6 @@ __device__ __forceinline__ int tk_wave_max(int v) {
     for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
     return v;
 }
-__device__ __forceinline__ long long tk_wave_sum64(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // row i of a 4 x 4 column-major transform applied to a point, in the header's order
 __device__ __forceinline__ float tk_row(const float *T, int i, float x, float y, float z) {
     const float a = T[i] * x;
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(SFT_NT) void sft_overlap_kernel(const TkArgs *args,
         }
         tk_count_pairs(key, lds, tab, O, K, M);
     }
-    warped = tk_wave_sum(warped);
+    warped = wave_sum(warped);
     if ((tid & 63) == 0 && warped) atomicAdd(&sums[blockIdx.y].n_warped, warped);
     if (lds) {
         __syncthreads();
@@ -308,7 +297,7 @@ __global__ __launch_bounds__(SFT_NT) void sft_commit_kernel(const TkArgs *args, 
         for (int j = 0; j < 3; j++) {
             lo[j] = tk_wave_min(join ? qv[j] : 0x7fffffff);
             hi[j] = tk_wave_max(join ? qv[j] : -0x7fffffff - 1);
-            sum[j] = tk_wave_sum64(join ? (long long)qv[j] : 0ll);
+            sum[j] = wave_sum(join ? (long long)qv[j] : 0ll);
         }
         if (lane == leader) {
             sft_track *r = rec + (k0 - 1);

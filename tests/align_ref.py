@@ -18,6 +18,15 @@ def _dot(a, b):
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
 
 
+def system_words(ok, J, r):
+    """the 32 int64 words of the system whose pairs are the elements with ok set: J the six float32 arrays of the row, r the
+    float32 residual; a = rint(clamp(J, -64, 64) * 4096), rho = rint(r * 65536), the sums in int64 (align, bodies and register)"""
+    with np.errstate(all="ignore"):
+        a = [np.where(ok, np.rint(np.fmin(np.fmax(Jk, F(-64)), F(64)) * F(4096)), F(0)).astype(np.int64) for Jk in J]
+        rho = np.where(ok, np.rint(r * F(65536)), F(0)).astype(np.int64)
+    return [int(ok.sum()), int((rho * rho).sum())] + [int((ak * rho).sum()) for ak in a] + [int((a[k] * a[l]).sum()) for k, l in PAIRS] + [0, 0, 0]
+
+
 def model_image(surfels, view, tick=1):
     """dict(drawn (rows, cols) bool, M and n: three (rows, cols) float32 planes each) of the map drawn from view"""
     surfels = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
@@ -67,11 +76,7 @@ def linearise(model, view, depth, b, params, D):
         r = _dot(n, d)
         ok &= np.abs(r) <= F(params.dist_max)
         c = (Q[1] * n[2] - n[1] * Q[2], Q[2] * n[0] - n[2] * Q[0], Q[0] * n[1] - n[0] * Q[1])
-        J = c + n
-        a = [np.where(ok, np.rint(np.fmin(np.fmax(Jk, F(-64)), F(64)) * F(4096)), F(0)).astype(np.int64) for Jk in J]
-        rho = np.where(ok, np.rint(r * F(65536)), F(0)).astype(np.int64)
-    w = [int(ok.sum()), int((rho * rho).sum())] + [int((ak * rho).sum()) for ak in a] + [int((a[k] * a[l]).sum()) for k, l in PAIRS] + [0, 0, 0]
-    return w
+    return system_words(ok, c + n, r)
 
 
 def step(w, damping, D):

@@ -90,9 +90,7 @@ def linearise(mdl, depth0, labels0, cam0, cam1, p, t, want, D):
         r = _dot(n, d)
         ok &= np.abs(r) <= F(p["dist_max"])
         J = _cross(Q, n) + n
-        a = [np.where(ok, np.rint(np.fmin(np.fmax(Jk, F(-64)), F(64)) * F(4096)), F(0)).astype(np.int64) for Jk in J]
-        rho = np.where(ok, np.rint(r * F(65536)), F(0)).astype(np.int64)
-    return [int(ok.sum()), int((rho * rho).sum())] + [int((ak * rho).sum()) for ak in a] + [int((a[k] * a[l]).sum()) for k, l in ar.PAIRS] + [0, 0, 0]
+    return ar.system_words(ok, J, r)
 
 
 def world_motion(pose0, pose1, D):

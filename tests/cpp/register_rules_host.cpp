@@ -4,7 +4,8 @@
 // parameters, the estimate, and the expected 32 words, counts and pairs -- and compares exactly; then the loops the table holds,
 // linearise and step in turn, against the expected estimates bit for bit. The surfels, the table's slots and the pairs lie in heap
 // blocks of exactly their size (the sanitizer sees a read or write beyond them), and the pairs have guard words around them. The
-// device runs the same text. Prints "ok <checks>".
+// device runs the same text. Before the table, quantise and accumulate of sf_p2p_system.h are called directly on the edge values of
+// the row and on 10 000 random rows, against the expressions written out here. Prints "ok <checks>".
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -87,11 +88,61 @@ static void linearise(const Case &c, const double *E, const int64_t *want, int w
     CHECK(std::memcmp(w, w2, sizeof(w)) == 0);
 }
 
+// quantise and accumulate of sf_p2p_system.h against the expressions written out here: the row J and the residual r
+static void system_row(const float J[6], float r) {
+    int a[6] = {7, 7, 7, 7, 7, 7}, rho = 7;
+    p2p::quantise(J, r, a, &rho);
+    for (int k = 0; k < 6; k++) CHECK(a[k] == (int)rintf(fminf(fmaxf(J[k], -64.f), 64.f) * 4096.f) && std::abs(a[k]) <= 1 << 18);
+    CHECK(rho == (int)rintf(r * 65536.f));
+    long long acc[p2p::WORDS], want[p2p::WORDS];
+    for (int f = 0; f < p2p::WORDS; f++) acc[f] = want[f] = 1000 + f;
+    for (int twice = 0; twice < 2; twice++) {
+        p2p::accumulate(acc, a, rho);
+        want[0] += 1;
+        want[1] += (long long)rho * rho;
+        int f = 8;
+        for (int k = 0; k < 6; k++) {
+            want[2 + k] += (long long)a[k] * rho;
+            for (int l = k; l < 6; l++) want[f++] += (long long)a[k] * a[l];
+        }
+        CHECK(f == p2p::FIELDS);
+    }
+    CHECK(std::memcmp(acc, want, sizeof(acc)) == 0);  // (the three reserved words are not touched)
+}
+
+static void system_rows() {
+    static_assert(p2p::FIELDS == 29 && p2p::WORDS == 32, "n, ss, g[6], H[21] and three reserved words");
+    // the edge values: +-64 exactly, beyond, +-0, NaN, and with them the largest r that dist_max <= 1 admits
+    const float edge[12] = {64.f, -64.f, 64.000008f, -64.000008f, 1e30f, -1e30f, INFINITY, -INFINITY, 0.f, -0.f, NAN, 63.999996f};
+    const float res[6] = {1.f, -1.f, 0.f, -0.f, 0.99999994f, 7.6293945e-06f};
+    for (int s = 0; s < 12; s++) {
+        float J[6];
+        for (int k = 0; k < 6; k++) J[k] = edge[(s + 5 * k) % 12];
+        system_row(J, res[s % 6]);
+    }
+    const float nan6[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
+    int a[6], rho;
+    p2p::quantise(nan6, 1.f, a, &rho);
+    for (int k = 0; k < 6; k++) CHECK(a[k] == -64 * 4096);  // fmaxf returns the bound
+    CHECK(rho == 65536);
+    uint64_t state = 0x9E3779B97F4A7C15ull;  // 10 000 random rows: J in [-80, 80), a third of them in [-1, 1); r in [-1, 1)
+    const auto uniform = [&state]() {
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        return (float)(state >> 40) * (1.0f / 8388608.0f) - 1.0f;
+    };
+    for (int t = 0; t < 10000; t++) {
+        float J[6];
+        for (int k = 0; k < 6; k++) J[k] = uniform() * ((t + k) % 3 ? 80.f : 1.f);
+        system_row(J, uniform());
+    }
+}
+
 int main(int argc, char **argv) {
     if (argc != 2 || !(in = std::fopen(argv[1], "rb"))) {
         std::printf("usage: register_rules_host <table>\n");
         return 2;
     }
+    system_rows();
     const int n_cases = rd1<int32_t>();
     for (int t = 0; t < n_cases; t++) {
         Case c;

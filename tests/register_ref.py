@@ -11,7 +11,6 @@ F = np.float32
 OK, FEW_PAIRS, DEGENERATE = 0, 1, 2
 NOT_PAIRED, NOT_SAMPLED = -1, -2
 SYSTEM_DTYPE = align_ref.SYSTEM_DTYPE
-PAIRS = align_ref.PAIRS
 DEFAULTS = dict(cell=0.1, dist_max=0.05, min_cos=0.5, min_confidence=0.0, damping=0.0, iterations=10, stride=1, min_pairs=64)
 IDENTITY = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
 
@@ -107,14 +106,10 @@ def linearise(dst, src, params, E, tab=None):
         r = _dot(n, dv)
         ok &= np.abs(r) <= F(params.dist_max)                                # 7
         cr = (Q[1] * n[2] - n[1] * Q[2], Q[2] * n[0] - n[2] * Q[0], Q[0] * n[1] - n[0] * Q[1])
-        J = cr + n
-        A = [np.where(ok, np.rint(np.fmin(np.fmax(Jk, F(-64)), F(64)) * F(4096)), F(0)).astype(np.int64) for Jk in J]
-        rho = np.where(ok, np.rint(r * F(65536)), F(0)).astype(np.int64)
         for x in (dd, r) + Q + mm + n + mn:
             assert x.dtype == np.float32
     pairs[idx] = np.where(ok, partner, NOT_PAIRED).astype(np.int32)
-    w = [int(ok.sum()), int((rho * rho).sum())] + [int((ak * rho).sum()) for ak in A] + [int((A[k] * A[l]).sum()) for k, l in PAIRS] + [0, 0, 0]
-    return w, int(idx.size), int((~inside).sum()), pairs
+    return align_ref.system_words(ok, cr + n, r), int(idx.size), int((~inside).sum()), pairs
 
 
 def start(T0):

@@ -69,6 +69,28 @@ def test_the_companion_host_sources_state_layout_block_and_refusals_once():
     assert re.findall(r'#include\s+"([^"]+)"', read("sf_call_block.h")) == ["sf_resources.h"]
 
 
+def test_the_point_to_plane_system_the_wave_sum_and_the_voxel_table_are_stated_once():
+    """the quantised row of the three point-to-plane solvers (sf_p2p_system.h), the shuffle sum over a wave (sf_device_common.h)
+    and the voxel table (sf_voxel_table.h) have one statement each, in the product and in the restatements of tests/"""
+    csrc = os.path.join(ROOT, "staticfusion_amd", "csrc")
+    read = lambda name: open(os.path.join(csrc, name)).read()
+    sources = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h", ".cpp"))]
+    other_quantities = ("sf_score.h", "sf_regions.h", "sf_keyframes.h")  # grey, b and gradient sums at the same scales
+    scales = [n for n in sources if n not in other_quantities and re.search(r"\b(4096|65536)\.0?f\b", read(n))]
+    assert scales == ["sf_p2p_system.h", "sf_splat.h"], scales  # (sf_splat.h: the reciprocal of a division by multiplication)
+    assert not re.search(r"rintf", read("sf_splat.h")) and len(re.findall(r"\b(?:4096|65536)\.0?f\b", read("sf_p2p_system.h"))) == 2
+    assert [n for n in sources if re.search(r"\+=\s*__shfl_xor\(", read(n))] == ["sf_device_common.h"]
+    for name in sources:  # no header is included inside a namespace: every #include stands outside all braces
+        src = re.sub(r"//.*|\"(?:[^\"\\\n]|\\.)*\"", "", read(name))
+        for m in re.finditer(r"^\s*#\s*include\b", src, re.M):
+            assert src[:m.start()].count("{") == src[:m.start()].count("}"), name
+    assert "sf_join.h" not in read("sf_register.h") and '#include "sf_voxel_table.h"' in read("sf_register.h")
+    assert '#include "sf_voxel_table.h"' in read("sf_join.h")
+    tests = os.path.join(ROOT, "tests")
+    refs = [n for n in sorted(os.listdir(tests)) if n.endswith("_ref.py") and re.search(r"np\.rint\([^\n]*4096", open(os.path.join(tests, n)).read())]
+    assert refs == ["align_ref.py", "keyframe_ref.py", "region_ref.py"], refs  # (the last two: the restatements of sf_keyframes.h and sf_regions.h)
+
+
 def test_the_host_sources_state_the_lifetime_of_a_handles_parts_once():
     """what is created from a handle (maps, keyframe databases, trackers, deformation graphs, closure builders) is entered in
     one list of the handle and orphaned, destroyed and refused by one piece of code each (sf_parts.h, sf_host.h)"""

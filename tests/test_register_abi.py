@@ -76,13 +76,19 @@ def test_header_table_and_exports_name_the_same_functions():
     assert re.search(r"^HOST_PARTS\s*\+=\s*register$", open(os.path.join(csrc, "Makefile")).read(), re.M)
     assert "sfg_*" in open(os.path.join(csrc, "sf_call_block.h")).read() and "sfg_registrar" in open(os.path.join(csrc, "sf_parts.h")).read()
     assert "sf_hip_register.hip" in open(os.path.join(csrc, "sf_host.h")).read()
-    # the rule text includes nothing of the library beyond the key of the join; the step is included, not restated
+    # the rule text includes nothing of the library beyond the key of the join and the system; the step is included, not restated
     rules = open(os.path.join(csrc, "sf_register_rules.h")).read()
-    assert re.findall(r'#include\s+"([^"]+)"', rules) == ["sf_join_key.h"] and "__global__" not in rules
+    assert re.findall(r'#include\s+"([^"]+)"', rules) == ["sf_join_key.h", "sf_p2p_system.h"] and "__global__" not in rules
+    system = open(os.path.join(csrc, "sf_p2p_system.h")).read()
+    assert not re.findall(r'#include\s+"([^"]+)"', system) and "__global__" not in system
     device = open(os.path.join(csrc, "sf_register.h")).read()
-    assert "sf_align_step.h" in device and "sfa_step_core(" in device and "LDL" not in device and "atomicAdd(float" not in device
+    shared = open(os.path.join(csrc, "sf_p2p_device.h")).read()  # the state, the reduction and the step's bookkeeping of the three solvers
+    assert '#include "sf_p2p_device.h"' in device and '#include "sf_align_step.h"' in shared and "sfa_step_core(" in shared
+    assert "LDL" not in device + shared and "atomicAdd(float" not in device + shared
     sources = device + open(os.path.join(csrc, "sf_hip_register.hip")).read()
-    assert "compare_exchange" not in sources and '#include "sf_join.h"' in device and "sfj_insert_kernel<true>" in sources  # the insert kernel is the join's
+    # the insert kernel is the voxel table's
+    assert "compare_exchange" not in sources and '#include "sf_voxel_table.h"' in device and "sf_join.h" not in device and "sfj_insert_kernel<true>" in sources
+    assert "compare_exchange" in open(os.path.join(csrc, "sf_voxel_table.h")).read() and "compare_exchange" not in open(os.path.join(csrc, "sf_join.h")).read()
 
 
 def test_the_oracle_binding_is_refused(ora):
